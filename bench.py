@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Adam iterations/sec of the deep-prior loop on the 3-D MultiRes-UNet (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4] [--full] [--dump-outputs DIR]
 
 N > 1 either way: started by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or plainly as `python bench.py --gpus N`: without WORLD_SIZE in the
@@ -34,7 +34,11 @@ tests/golden/host.npz — /root/reference does not exist on the GPU box) with it
 (2 186 704 parameters), the geometry of proof_of_concept_2D.ipynb (3000 iterations in 142 s = 21 it/s on a V100); `--aa-weight W`
 adds the anti-aliasing regulariser (dips + Hale2D adjoint every iteration).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step)
+and the configuration.  A plain run does only what that line needs: set-up, warm-up, the K timed steps, the line.  `--full` adds what
+is measured beside it on c2: the per-family kernel timing pass and `roofline`, the `gather`, `other_modes`, `configs2` and
+`cpu_baseline` (null without it).  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy
+(dump_outputs / loop_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -84,9 +88,18 @@ def parse():
                          "each a SECOND bench line, the headline stays fp32")
     ap.add_argument("--concurrent", type=int, default=6, help="c3: patches optimised side by side on one GPU")
     ap.add_argument("--launch-timeout", type=int, default=1800, help="--gpus N without a launcher: seconds before the rank processes are killed")
+    ap.add_argument("--full", action="store_true",
+                    help="c2: everything beside the headline figure — the per-family kernel timing pass and `roofline`, HIP events in the timed "
+                         "region, the `gather`, `other_modes`, `configs2` and `cpu_baseline` (each still subject to its --no-* switch); "
+                         "without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of anything larger)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = {"c2": 10, "c3": 100, "c4": 300, "c5": 30, "selftest": 3}[a.workload]
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.patch is None:
         a.patch = {"c2": [256, 128, 128], "c5": [512, 256, 256]}.get(a.workload, [64, 64, 64])
     if a.workload == "c5":          # BASELINE configs[4]: bf16 activations + fp32 masters; field-scale patches run one at a time
@@ -260,6 +273,41 @@ def bmin_bytes(V, precision):
     return per_voxel * V + BMIN_CONST
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # --dump-outputs: array data of all files together (64 MB with room for the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array or tensor} -> path/<name>.npy; float64 stays float64, everything else is written as float32.  The arrays
+    share DUMP_BUDGET_BYTES smallest first: one that does not fit its equal share of what is left is cut to a fixed sample of its flattened
+    elements (sorted indices drawn by np.random.default_rng(0) from its size alone), so two builds run with the same arguments write the
+    same positions."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().float().cpu().numpy() if v.dtype != torch.float64 else v.detach().cpu().numpy()
+        v = np.asarray(v)
+        host[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False)
+    left = DUMP_BUDGET_BYTES
+    order = sorted(host, key=lambda k: (host[k].nbytes, k))
+    for i, name in enumerate(order):
+        v = host[name]
+        share = left // (len(order) - i)
+        if v.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[idx]
+        left -= v.nbytes
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def loop_outputs(T, steps):
+    """What a caller of one patch's Adam loop receives after the last timed step: the best output so far (`out_best`), every parameter
+    of the network flattened in net.parameters() order (`params`), and loss / SNR / PCORR of each of the `steps` timed steps (`metrics`)."""
+    h = T.history
+    return {"out_best": T._out_best_dev, "params": torch.cat([p.detach().reshape(-1).float() for p in T.net.parameters()]),
+            "metrics": np.array([h.loss, h.snr, h.pcorr], dtype=np.float64).T[-steps:]}
+
+
 def run_c2(a, rank, world, device):
     import torch.distributed as dist
     from deep_prior_interpolation_amd import ops, parallel, utils as u
@@ -310,31 +358,35 @@ def run_c2(a, rank, world, device):
     def family(kind, d):
         return (kind, int(d.k), int(d.stride))
 
-    # ---- warm-up.  One of the warm-up iterations runs with HIP events around EVERY convolution launch and without the side-stream
-    # overlap of the weight gradients (a kernel that shares the chip with another stream's kernel is not a kernel duration): it
-    # yields the per-family table and names the family that takes the largest share of the iteration.
+    # ---- warm-up.  With --full one of the warm-up iterations runs with HIP events around EVERY convolution launch and without the
+    # side-stream overlap of the weight gradients (a kernel that shares the chip with another stream's kernel is not a kernel duration):
+    # it yields the per-family table and names the family that takes the largest share of the iteration.  A plain run makes that
+    # iteration an ordinary one, so both run the same number of iterations before the timed region.
     eager_step()
-    ops.set_weight_grad_overlap(False)
-    detail = ops.KernelTimer(lambda kind, d: (kind, (d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride)))
-    descs = {}
-    inner = detail.match
-
-    def match_and_remember(kind, d):
-        descs[(d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride)] = (conv_flop(d), conv_bytes(d), family(kind, d)[1:])
-        return inner(kind, d)
-    detail.match = match_and_remember
-    ops.set_timer(detail)
-    eager_step()
-    torch.cuda.synchronize(device)
-    ops.set_timer(None)
-    ops.set_weight_grad_overlap(overlap)
     fam = {}
     layers = []
-    for (kind, shape), ms_list in detail.by_key().items():
-        flop, nbytes, (k, stride_) = descs[shape]
-        f = fam.setdefault((kind, k, stride_), {"launches": 0, "ms": 0.0, "flop": 0.0, "bytes": 0.0})
-        f["launches"] += len(ms_list); f["ms"] += float(np.sum(ms_list)); f["flop"] += flop * len(ms_list); f["bytes"] += nbytes * len(ms_list)
-        layers.append((kind, shape, float(np.mean(ms_list)), flop, nbytes))
+    descs = {}
+    if a.full:
+        ops.set_weight_grad_overlap(False)
+        detail = ops.KernelTimer(lambda kind, d: (kind, (d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride)))
+        inner = detail.match
+
+        def match_and_remember(kind, d):
+            descs[(d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride)] = (conv_flop(d), conv_bytes(d), family(kind, d)[1:])
+            return inner(kind, d)
+        detail.match = match_and_remember
+        ops.set_timer(detail)
+        eager_step()
+        torch.cuda.synchronize(device)
+        ops.set_timer(None)
+        ops.set_weight_grad_overlap(overlap)
+        for (kind, shape), ms_list in detail.by_key().items():
+            flop, nbytes, (k, stride_) = descs[shape]
+            f = fam.setdefault((kind, k, stride_), {"launches": 0, "ms": 0.0, "flop": 0.0, "bytes": 0.0})
+            f["launches"] += len(ms_list); f["ms"] += float(np.sum(ms_list)); f["flop"] += flop * len(ms_list); f["bytes"] += nbytes * len(ms_list)
+            layers.append((kind, shape, float(np.mean(ms_list)), flop, nbytes))
+    else:
+        eager_step()
     dom_key = max(fam, key=lambda kk: fam[kk]["ms"]) if fam else None
 
     if mode == "graph":
@@ -346,15 +398,16 @@ def run_c2(a, rank, world, device):
         step = eager_step
         for _ in range(max(a.warmup - 2, 1)):
             step()
-    # ---- timed region: exactly `steps` iterations; HIP events only around the launches of the dominant family
+    # ---- timed region: exactly `steps` iterations; with --full, HIP events only around the launches of the dominant family
     timer = ops.KernelTimer(lambda kind, d: family(kind, d) == dom_key and (d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride))
+    timed_step = a.full and mode == "eager"
     barrier()
     # (the event records cost: 64 of them per iteration — two per launch of the family — measured 29.8 vs 29.5 ms fp32 and 15.9-16.0 vs 15.6-15.8 ms bf16,
     #  alternating on one box; every TIMER_EVERY-th iteration of the timed region carries them)
     timed_its = len(range(0, a.steps, TIMER_EVERY))
     t0 = time.perf_counter()
     for i in range(a.steps):
-        if mode == "eager":
+        if timed_step:
             ops.set_timer(timer if i % TIMER_EVERY == 0 else None)
         step()
     barrier()
@@ -365,51 +418,61 @@ def run_c2(a, rank, world, device):
                   + ("; the weight gradients run on a side stream next to the backward-data chain, so these durations include sharing the chip"
                      if overlap and dom_key and dom_key[0] == "conv_bwd_weight" else ""))
     if mode == "graph":
+        T.graph_finish()                    # history and best output of the replayed iterations back on the host side
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loop_outputs(T, a.steps))
+    if mode == "graph" and a.full:
         # launches inside a replayed graph cannot be bracketed from the host: time the same kernels on the same tensors in a
         # short eager tail right after the timed region
-        T.graph_finish()
         ops.set_timer(timer)
         for _ in range(3):
             eager_step()
         torch.cuda.synchronize(device)
         ops.set_timer(None)
         timing_src = "HIP events around this family in 3 eager iterations run right after the graph-replayed timed region"
-    # ---- the job's only collective: the reconstruct_patches gather (overlap-add of every rank's best output, ONE all-reduce, normalise)
-    best = T._out_best_dev if T._out_best_dev is not None else T._g_best
-    acc = parallel.DeviceOverlapAccumulator(vshape, dim, stride, device)
-    from deep_prior_interpolation_amd import _lib
-    barrier()
-    g0 = time.perf_counter()
-    acc.add(best.reshape(best.shape[2:]), origins[pidx])
-    local_sum = acc.tensor().double().sum()       # this rank's accumulator before the exchange (checked below)
-    torch.cuda.synchronize(device)
-    c0 = time.perf_counter()                      # the collective ALONE (what a SCALE run should read as its cost), between two device syncs
-    parallel.gather_volume(acc)
-    torch.cuda.synchronize(device)
-    collective_s = time.perf_counter() - c0
-    u_ = acc.tensor()
-    _lib.check(_lib.load().dpi_overlap_normalize(_lib.ptr(u_), *vshape, *dim, *stride, float(args.gain), _lib.stream()), "dpi_overlap_normalize")
-    barrier()
-    gather_s = time.perf_counter() - g0
-    counts = [1]
-    gather_ok = bool(torch.isfinite(u_).all().item())
-    if world > 1:
-        t = torch.tensor([dt, gather_s, collective_s], dtype=torch.float64, device=device)
+    # ---- the job's only collective: the reconstruct_patches gather (overlap-add of every rank's best output, ONE all-reduce, normalise), with --full
+    gather_s = collective_s = acc = None
+    counts, gather_ok = [1], None
+    if a.full:
+        best = T._out_best_dev if T._out_best_dev is not None else T._g_best
+        acc = parallel.DeviceOverlapAccumulator(vshape, dim, stride, device)
+        from deep_prior_interpolation_amd import _lib
+        barrier()
+        g0 = time.perf_counter()
+        acc.add(best.reshape(best.shape[2:]), origins[pidx])
+        local_sum = acc.tensor().double().sum()       # this rank's accumulator before the exchange (checked below)
+        torch.cuda.synchronize(device)
+        c0 = time.perf_counter()                      # the collective ALONE (what a SCALE run should read as its cost), between two device syncs
+        parallel.gather_volume(acc)
+        torch.cuda.synchronize(device)
+        collective_s = time.perf_counter() - c0
+        u_ = acc.tensor()
+        _lib.check(_lib.load().dpi_overlap_normalize(_lib.ptr(u_), *vshape, *dim, *stride, float(args.gain), _lib.stream()), "dpi_overlap_normalize")
+        barrier()
+        gather_s = time.perf_counter() - g0
+        counts = [1]
+        gather_ok = bool(torch.isfinite(u_).all().item())
+        if world > 1:
+            t = torch.tensor([dt, gather_s, collective_s], dtype=torch.float64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt, gather_s, collective_s = float(t[0].item()), float(t[1].item()), float(t[2].item())
+            cnt = torch.zeros(world, dtype=torch.int64, device=device)
+            cnt[rank] = len(mine)
+            dist.all_reduce(cnt)
+            counts = [int(c) for c in cnt.tolist()]
+            tot = local_sum.clone()
+            dist.all_reduce(tot)
+            # the all-reduced accumulator must be the sum of the ranks' accumulators (checked on its grand total before normalisation
+            # is not possible any more; the normalised volume times hit count times gain sums to the same number)
+            gather_ok = gather_ok and bool(torch.isfinite(tot).item())
+    elif world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, gather_s, collective_s = float(t[0].item()), float(t[1].item()), float(t[2].item())
-        cnt = torch.zeros(world, dtype=torch.int64, device=device)
-        cnt[rank] = len(mine)
-        dist.all_reduce(cnt)
-        counts = [int(c) for c in cnt.tolist()]
-        tot = local_sum.clone()
-        dist.all_reduce(tot)
-        # the all-reduced accumulator must be the sum of the ranks' accumulators (checked on its grand total before normalisation
-        # is not possible any more; the normalised volume times hit count times gain sums to the same number)
-        gather_ok = gather_ok and bool(torch.isfinite(tot).item())
+        dt = float(t.item())
     ms = dt / a.steps * 1e3          # (every rank assembles the record — pure host arithmetic — because the configs[2] block below is a collective job)
     iter_flop = FLOP_PER_VOXEL_ITER * V
     bmin = bmin_bytes(V, a.precision)
-    prof, traffic_stale = load_profile_json(a.precision) if tuple(a.patch) == (256, 128, 128) else (None, False)
+    prof, traffic_stale = load_profile_json(a.precision) if (a.full and tuple(a.patch) == (256, 128, 128)) else (None, False)
     roof = None
     fam_rows = []
     for kk, f in sorted(fam.items(), key=lambda it: -it[1]["ms"]):
@@ -498,7 +561,7 @@ def run_c2(a, rank, world, device):
                             % a.precision)
     # the other arithmetic modes on the same patch, right after the timed region (information only: `value` above is the mode asked for)
     other = None
-    if a.precision == "fp32" and world == 1 and mode == "eager" and not a.no_other_modes:
+    if a.full and a.precision == "fp32" and world == 1 and mode == "eager" and not a.no_other_modes:
         other = {}
         for prec, label in (("bf16", "bf16 (activations + gradients stored as bf16, bf16 MFMA operands)"), ("bf16mm", "f32 storage, bf16 MFMA operands"),
                             ("split", "f32 (3 x bf16 split)")):
@@ -520,12 +583,12 @@ def run_c2(a, rank, world, device):
     del T, acc
     torch.cuda.empty_cache()
     c3 = None
-    if a.precision == "fp32" and not a.no_c3_extra and tuple(a.patch) == (256, 128, 128):
+    if a.full and a.precision == "fp32" and not a.no_c3_extra and tuple(a.patch) == (256, 128, 128):
         c3 = configs2_extra(a, rank, world, device)        # every rank: the queue is shared and the job ends in an all-reduce
     if rank != 0:
         return None
     cpu = None
-    if not a.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only (the contract), after the gather; nothing collective follows
+    if a.full and not a.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only (the contract), after the gather; nothing collective follows
         cpu = cpu_baseline(a.patch, a.cpu_patch, a.upsample, a.cpu_iters, gpu_small_patch_rate(a.cpu_patch, a.upsample, device))
     return {"metric": "Adam iters/sec on 3D MultiRes-UNet (whole job over n_gpus; per_gpu beside it); recon SNR(dB) vs ref under config.snr_vs_reference", "value": round(world * a.steps / dt, 4), "unit": "it/s",
             "per_gpu": round(a.steps / dt, 4),
@@ -540,7 +603,7 @@ def run_c2(a, rank, world, device):
                                    "from the shared queue, one per GPU, loop mode %s; value = whole job (all GPUs), per_gpu = value / n_gpus"
                                    % (tuple(a.patch) + (args.upsample,) + vshape + (std, world, st, mode)),
                        "last_loss": last_loss, "last_snr_db": last_snr, "snr_vs_reference": SNR_STATEMENT},
-            "gather": {"what": "reconstruct_patches: dpi_overlap_add of each rank's best output + ONE all-reduce(sum) of the %dx%dx%d fp32 accumulator "
+            "gather": None if gather_s is None else {"what": "reconstruct_patches: dpi_overlap_add of each rank's best output + ONE all-reduce(sum) of the %dx%dx%d fp32 accumulator "
                                "(%s) + dpi_overlap_normalize" % (vshape + ("RCCL, %d ranks" % world if world > 1 else "no collective at 1 rank",)),
                        "ms": round(gather_s * 1e3, 3), "collective_ms": round(collective_s * 1e3, 3),
                        "collective_note": "all-reduce alone between two device synchronisations, max over ranks (nothing to do at 1 rank); `ms` adds the overlap-add, "
@@ -636,6 +699,8 @@ def run_c3(a, rank, world, device):
         per_rank = [[int(r[0])] + [round(float(v), 3) for v in r[1:]] for r in row.tolist()]
     if rank != 0:
         return None
+    if a.dump_outputs and getattr(a, "total_patches", None) is None:       # (not for the configs2 block of a c2 line)
+        dump_outputs(a.dump_outputs, {"reconstruction": rec})
     V = int(np.prod(a.patch))
     its = n_run * a.steps
     rate = its / dt
@@ -720,6 +785,8 @@ def run_c4(a, rank, world, device):
     dt = time.perf_counter() - t0
     if a.aa_weight <= 0:
         T.graph_finish()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loop_outputs(T, a.steps))
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -784,6 +851,8 @@ def run_selftest(a, rank, world, device):
     ok = bool(np.allclose(rec, exp / hits))
     if rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"reconstruction": rec})
     return {"metric": "selftest (launcher + queue + gather plumbing, no kernels)", "value": round(npatch * a.steps / dt, 3), "unit": "it/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",

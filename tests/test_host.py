@@ -300,7 +300,7 @@ def test_get_net_reaches_the_2d_skip_net_for_configs3(golden):
     assert not isinstance(get_net(parse_arguments(["--imgdir", "x", "--datadim", "2d"]), 1), Skip)          # the default stays MulResUnet
 
 
-def test_branch_stream_host_logic_knows_the_deep_branch_width():
+def test_branch_stream_host_logic_knows_the_deep_branch_width(monkeypatch):
     """Round 5: the ResPath half of a level join is started on the branch stream BEFORE the deeper U has run (ops.skip_begin), so the concat
     buffer must be sized from the module tree: `_deep_channels` = the channels the deeper branch hands to its Upsample = what the decoder
     block behind the join expects beyond the skip width (reference mulresunet.py:227-243).  Also: outside an Interpolator iteration the
@@ -325,6 +325,8 @@ def test_branch_stream_host_logic_knows_the_deep_branch_width():
                         walk(m)
     walk(net)
     assert seen == 4                                            # four level joins in the default five-scale net
+    # the switch as a fresh process has it: a big-patch GPU test earlier in the same session may have left it on (ops.set_weight_grad_overlap)
+    monkeypatch.setattr(ops, "OVERLAP_WEIGHT_GRADS", os.environ.get("DPI_OVERLAP_WGRAD", "0") == "1")
     assert ops.JOIN_AT == "step" and not ops._in_iteration[0]
     assert not ops.branch_on()                                  # no iteration, no weight-gradient overlap: the serial schedule
     ops.begin_iteration()
