@@ -15,7 +15,7 @@ class DpiError(RuntimeError):
     pass
 
 
-ABI_VERSION = 404      # dpi_set_option replaces the ten dpi_set_* tuning exports (404); include/dpi_hip.h: dpi_conv_desc starts with its own size (300); dpi_conv_fwd_ws / dpi_conv_bwd_data_ws (301); `io` + the *_io entry points (400); dpi_pack_* (401); dpi_pack_forget (402); dpi_join_bwd (403)
+ABI_VERSION = 405      # dpi_hale_sections / dpi_structure_tensor_sections (405); dpi_set_option replaces the ten dpi_set_* tuning exports (404); include/dpi_hip.h: dpi_conv_desc starts with its own size (300); dpi_conv_fwd_ws / dpi_conv_bwd_data_ws (301); `io` + the *_io entry points (400); dpi_pack_* (401); dpi_pack_forget (402); dpi_join_bwd (403)
 
 # dpi_conv_desc.io bits / the `io` masks of the *_io entry points (bf16 storage of activations, BASELINE configs[4])
 IO_X_BF16, IO_Y_BF16, IO_DY_BF16, IO_DX_BF16 = 1, 2, 4, 8
@@ -98,6 +98,8 @@ SIGNATURES = {
     "dpi_hale2d": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _P, _P]),
     "dpi_structure_tensor": (_I, [_P, _Z, _I, _I, _F, _F, _P, _P, _P, _P]),
     "dpi_dips": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
+    "dpi_hale_sections": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),                     # ABI 405: the add-on on 3-D patches
+    "dpi_structure_tensor_sections": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     "dpi_max_ws_floats": (_Z, [_Z]),
     "dpi_scaled_max": (_I, [_P, _Z, _F, _P, _P, _P]),
     "dpi_threshold": (_I, [_P, _Z, _P, _P, _P]),

@@ -49,19 +49,25 @@ __global__ __launch_bounds__(256) void diff_axis_kernel(const float* __restrict_
 // (it re-applies the FORWARD difference instead of the divergence, and crosses the axes; reproduced as is).  One thread per
 // sample evaluates p1 at (i,j),(i,j+1) and p2 at (i,j),(i+1,j) from the 3x3 neighbourhood: 4 reads of x and 3 coefficient
 // planes per sample, all served by L1/L2 after the first touch.
+// The per-sample arithmetic (hale_pv / hale_qv, on values) is shared with the vertical sections of a 3-D patch below, so both
+// paths give the same bits for the same section.
 struct HaleP {
   float p1, p2;
 };
+// p1, p2 at one sample from x there (x0), at its v / h neighbours (xv, xh; used only where hv / hh: inside the section)
+__device__ __forceinline__ HaleP hale_pv(float x0, float xv, float xh, bool hv, bool hh, float a, float b, float c) {
+  const float gv = hv ? xv - x0 : 0.f;
+  const float gh = hh ? xh - x0 : 0.f;
+  HaleP r;
+  r.p1 = a * gv + b * gh;
+  r.p2 = b * gv + c * gh;
+  return r;
+}
 __device__ __forceinline__ HaleP hale_p(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
                                         const float* __restrict__ c, size_t base, int i, int j, int H, int W) {
   const size_t o = base + (size_t)i * W + j;
-  const float x0 = x[o];
-  const float gv = i <= H - 2 ? x[o + W] - x0 : 0.f;
-  const float gh = j <= W - 2 ? x[o + 1] - x0 : 0.f;
-  HaleP r;
-  r.p1 = a[o] * gv + b[o] * gh;
-  r.p2 = b[o] * gv + c[o] * gh;
-  return r;
+  const bool hv = i <= H - 2, hh = j <= W - 2;
+  return hale_pv(x[o], hv ? x[o + W] : 0.f, hh ? x[o + 1] : 0.f, hv, hh, a[o], b[o], c[o]);
 }
 __global__ __launch_bounds__(256) void hale2d_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
                                                          const float* __restrict__ c, size_t total, int H, int W, float* __restrict__ y) {
@@ -79,16 +85,19 @@ __global__ __launch_bounds__(256) void hale2d_fwd_kernel(const float* __restrict
 // transpose: with r1 = Dh^T g, r2 = Dv^T g (D^T u)(k) = u(k-1)[k >= 1] - u(k)[k <= n-2]:
 //     q1 = a*r1 + b*r2,  q2 = b*r1 + c*r2,   x = -( Dv^T q1 + Dh^T q2 )
 __device__ __forceinline__ float dT(float prev, float cur, int k, int n) { return (k >= 1 ? prev : 0.f) - (k <= n - 2 ? cur : 0.f); }
+// q1, q2 at sample (i,j) of an H x W section from g there (g0) and at its h / v predecessors (gh, gv)
+__device__ __forceinline__ HaleP hale_qv(float g0, float gh, float gv, int i, int j, int H, int W, float a, float b, float c) {
+  const float r1 = dT(gh, g0, j, W);
+  const float r2 = dT(gv, g0, i, H);
+  HaleP r;
+  r.p1 = a * r1 + b * r2;
+  r.p2 = b * r1 + c * r2;
+  return r;
+}
 __device__ __forceinline__ HaleP hale_q(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ b,
                                         const float* __restrict__ c, size_t base, int i, int j, int H, int W) {
   const size_t o = base + (size_t)i * W + j;
-  const float g0 = g[o];
-  const float r1 = dT(j >= 1 ? g[o - 1] : 0.f, g0, j, W);
-  const float r2 = dT(i >= 1 ? g[o - W] : 0.f, g0, i, H);
-  HaleP r;
-  r.p1 = a[o] * r1 + b[o] * r2;
-  r.p2 = b[o] * r1 + c[o] * r2;
-  return r;
+  return hale_qv(g[o], j >= 1 ? g[o - 1] : 0.f, i >= 1 ? g[o - W] : 0.f, i, j, H, W, a[o], b[o], c[o]);
 }
 __global__ __launch_bounds__(256) void hale2d_adj_kernel(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ b,
                                                          const float* __restrict__ c, size_t total, int H, int W, float* __restrict__ xo) {
@@ -100,6 +109,145 @@ __global__ __launch_bounds__(256) void hale2d_adj_kernel(const float* __restrict
     const float q1_up = i >= 1 ? hale_q(g, a, b, c, base, i - 1, j, H, W).p1 : 0.f;
     const float q2_left = j >= 1 ? hale_q(g, a, b, c, base, i, j - 1, H, W).p2 : 0.f;
     xo[idx] = -(dT(q1_up, q.p1, i, H) + dT(q2_left, q.p2, j, W));
+  }
+}
+
+// ---- Hale2D on both families of vertical sections of a [C][T][X][Y] patch ----------------------------------------------
+// (t,x) sections: v = t (stride X*Y), h = x (stride Y); (t,y) sections: v = t, h = y (stride 1).  Coefficients: six [C][T][X][Y]
+// fields a, b, c of the (t,x) family, then of the (t,y) family.  One thread owns V consecutive samples of a y-row (float4 when
+// Y % 4 == 0) and reads the rows its 3x3 neighbourhoods touch; the rows of the neighbouring x / t come back through L2 / MALL,
+// so HBM sees x, the six coefficient fields and the two outputs once: 36 bytes per sample either way.
+template <int V>
+__device__ __forceinline__ void ld_row(const float* __restrict__ p, size_t o, bool ok, float* r) {
+  if (V == 4) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) v = *reinterpret_cast<const float4*>(p + o);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+  } else {
+    r[0] = ok ? p[o] : 0.f;
+  }
+}
+template <int V>
+__device__ __forceinline__ void st_row(float* __restrict__ p, size_t o, const float* r) {
+  if (V == 4) *reinterpret_cast<float4*>(p + o) = make_float4(r[0], r[1], r[2], r[3]);
+  else p[o] = r[0];
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void hale_sections_fwd_kernel(const float* __restrict__ x, const float* __restrict__ coef, unsigned rows, int T,
+                                                                int X, int Y, size_t n, float* __restrict__ y) {
+  const unsigned nq = (unsigned)Y / V, total = rows * nq;
+  const size_t sv = (size_t)X * Y;
+  const float *a0 = coef, *b0 = coef + n, *c0 = coef + 2 * n, *a1 = coef + 3 * n, *b1 = coef + 4 * n, *c1 = coef + 5 * n;
+  for (unsigned idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+    const unsigned r = idx / nq, q = idx - r * nq;
+    const int xi = (int)(r % (unsigned)X), t = (int)(r / (unsigned)X % (unsigned)T), y0 = (int)q * V;
+    const size_t o = (size_t)r * Y + y0;
+    const bool t1 = t <= T - 2, t2 = t <= T - 3, x1 = xi <= X - 2, x2 = xi <= X - 3;
+    const bool e1 = y0 + V < Y, e2 = y0 + V + 1 < Y;           // the samples past the row segment along y exist
+    // x at (t,x) [+2 along y], (t+1,x) [+1], (t+2,x), (t,x+1), (t+1,x+1), (t,x+2)
+    float xa[V + 2], xb[V + 1], xc[V], xd[V], xe[V], xf[V];
+    ld_row<V>(x, o, true, xa);
+    xa[V] = e1 ? x[o + V] : 0.f;
+    xa[V + 1] = e2 ? x[o + V + 1] : 0.f;
+    ld_row<V>(x, o + sv, t1, xb);
+    xb[V] = t1 && e1 ? x[o + sv + V] : 0.f;
+    ld_row<V>(x, o + 2 * sv, t2, xc);
+    ld_row<V>(x, o + Y, x1, xd);
+    ld_row<V>(x, o + sv + Y, t1 && x1, xe);
+    ld_row<V>(x, o + 2 * (size_t)Y, x2, xf);
+    // (t,x) coefficients at (t,x), (t,x+1), (t+1,x); (t,y) coefficients at (t,x) [+1 along y], (t+1,x)
+    float A[V], B[V], Cc[V], Ah[V], Bh[V], Ch[V], Av[V], Bv[V], Cv[V];
+    ld_row<V>(a0, o, true, A); ld_row<V>(b0, o, true, B); ld_row<V>(c0, o, true, Cc);
+    ld_row<V>(a0, o + Y, x1, Ah); ld_row<V>(b0, o + Y, x1, Bh); ld_row<V>(c0, o + Y, x1, Ch);
+    ld_row<V>(a0, o + sv, t1, Av); ld_row<V>(b0, o + sv, t1, Bv); ld_row<V>(c0, o + sv, t1, Cv);
+    float P[V + 1], Q[V + 1], R[V + 1], Pv[V], Qv[V], Rv[V];
+    ld_row<V>(a1, o, true, P); ld_row<V>(b1, o, true, Q); ld_row<V>(c1, o, true, R);
+    P[V] = e1 ? a1[o + V] : 0.f;
+    Q[V] = e1 ? b1[o + V] : 0.f;
+    R[V] = e1 ? c1[o + V] : 0.f;
+    ld_row<V>(a1, o + sv, t1, Pv); ld_row<V>(b1, o + sv, t1, Qv); ld_row<V>(c1, o + sv, t1, Rv);
+    float out0[V], out1[V];
+#pragma unroll
+    for (int l = 0; l < V; ++l) {
+      // (t,x) section: p at (t,x), p1 at (t,x+1), p2 at (t+1,x)
+      HaleP p = hale_pv(xa[l], xb[l], xd[l], t1, x1, A[l], B[l], Cc[l]);
+      float ata1 = 0.f, ata2 = 0.f;
+      if (x1) ata1 = hale_pv(xd[l], xe[l], xf[l], t1, x2, Ah[l], Bh[l], Ch[l]).p1 - p.p1;
+      if (t1) ata2 = hale_pv(xb[l], xc[l], xe[l], t2, x1, Av[l], Bv[l], Cv[l]).p2 - p.p2;
+      out0[l] = -(ata1 + ata2);
+      // (t,y) section: p at (t,y), p1 at (t,y+1), p2 at (t+1,y)
+      const int j = y0 + l;
+      const bool y1 = j <= Y - 2, y2 = j <= Y - 3;
+      p = hale_pv(xa[l], xb[l], xa[l + 1], t1, y1, P[l], Q[l], R[l]);
+      ata1 = 0.f;
+      ata2 = 0.f;
+      if (y1) ata1 = hale_pv(xa[l + 1], xb[l + 1], xa[l + 2], t1, y2, P[l + 1], Q[l + 1], R[l + 1]).p1 - p.p1;
+      if (t1) ata2 = hale_pv(xb[l], xc[l], xb[l + 1], t2, y1, Pv[l], Qv[l], Rv[l]).p2 - p.p2;
+      out1[l] = -(ata1 + ata2);
+    }
+    st_row<V>(y, o, out0);
+    st_row<V>(y, n + o, out1);
+  }
+}
+
+// adjoint: x = L_tx^T g[0] + L_ty^T g[1], each term as hale2d_adj_kernel evaluates it on its section
+template <int V>
+__global__ __launch_bounds__(256) void hale_sections_adj_kernel(const float* __restrict__ g, const float* __restrict__ coef, unsigned rows, int T,
+                                                                int X, int Y, size_t n, float* __restrict__ xo) {
+  const unsigned nq = (unsigned)Y / V, total = rows * nq;
+  const size_t sv = (size_t)X * Y;
+  const float *a0 = coef, *b0 = coef + n, *c0 = coef + 2 * n, *a1 = coef + 3 * n, *b1 = coef + 4 * n, *c1 = coef + 5 * n;
+  const float *g0 = g, *g1 = g + n;
+  for (unsigned idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+    const unsigned r = idx / nq, q = idx - r * nq;
+    const int xi = (int)(r % (unsigned)X), t = (int)(r / (unsigned)X % (unsigned)T), y0 = (int)q * V;
+    const size_t o = (size_t)r * Y + y0;
+    const bool t1 = t >= 1, t2 = t >= 2, x1 = xi >= 1, x2 = xi >= 2;
+    // g[0] at (t,x), (t,x-1), (t-1,x), (t-1,x-1), (t-2,x), (t,x-2)
+    float ga[V], gb[V], gc[V], gd[V], ge[V], gf[V];
+    ld_row<V>(g0, o, true, ga);
+    ld_row<V>(g0, o - (x1 ? Y : 0), x1, gb);
+    ld_row<V>(g0, o - (t1 ? sv : 0), t1, gc);
+    ld_row<V>(g0, o - (t1 && x1 ? sv + Y : 0), t1 && x1, gd);
+    ld_row<V>(g0, o - (t2 ? 2 * sv : 0), t2, ge);
+    ld_row<V>(g0, o - (x2 ? 2 * (size_t)Y : 0), x2, gf);
+    // g[1] at (t,x) [-2 along y: ha[k] = y0 - 2 + k], (t-1,x) [-1: hb[k] = y0 - 1 + k], (t-2,x)
+    float ha[V + 2], hb[V + 1], hc[V];
+    ha[0] = y0 >= 2 ? g1[o - 2] : 0.f;
+    ha[1] = y0 >= 1 ? g1[o - 1] : 0.f;
+    ld_row<V>(g1, o, true, ha + 2);
+    hb[0] = t1 && y0 >= 1 ? g1[o - sv - 1] : 0.f;
+    ld_row<V>(g1, o - (t1 ? sv : 0), t1, hb + 1);
+    ld_row<V>(g1, o - (t2 ? 2 * sv : 0), t2, hc);
+    // (t,x) coefficients at (t,x), (t-1,x), (t,x-1); (t,y) coefficients at (t,x) [-1 along y], (t-1,x)
+    float A[V], B[V], Cc[V], Au[V], Bu[V], Cu[V], Al[V], Bl[V], Cl[V];
+    ld_row<V>(a0, o, true, A); ld_row<V>(b0, o, true, B); ld_row<V>(c0, o, true, Cc);
+    ld_row<V>(a0, o - (t1 ? sv : 0), t1, Au); ld_row<V>(b0, o - (t1 ? sv : 0), t1, Bu); ld_row<V>(c0, o - (t1 ? sv : 0), t1, Cu);
+    ld_row<V>(a0, o - (x1 ? Y : 0), x1, Al); ld_row<V>(b0, o - (x1 ? Y : 0), x1, Bl); ld_row<V>(c0, o - (x1 ? Y : 0), x1, Cl);
+    float P[V + 1], Q[V + 1], R[V + 1], Pu[V], Qu[V], Ru[V];
+    P[0] = y0 >= 1 ? a1[o - 1] : 0.f;
+    Q[0] = y0 >= 1 ? b1[o - 1] : 0.f;
+    R[0] = y0 >= 1 ? c1[o - 1] : 0.f;
+    ld_row<V>(a1, o, true, P + 1); ld_row<V>(b1, o, true, Q + 1); ld_row<V>(c1, o, true, R + 1);
+    ld_row<V>(a1, o - (t1 ? sv : 0), t1, Pu); ld_row<V>(b1, o - (t1 ? sv : 0), t1, Qu); ld_row<V>(c1, o - (t1 ? sv : 0), t1, Ru);
+    float out[V];
+#pragma unroll
+    for (int l = 0; l < V; ++l) {
+      // (t,x) section: q at (t,x), q1 at (t-1,x), q2 at (t,x-1)
+      HaleP qq = hale_qv(ga[l], gb[l], gc[l], t, xi, T, X, A[l], B[l], Cc[l]);
+      float q1_up = t1 ? hale_qv(gc[l], gd[l], ge[l], t - 1, xi, T, X, Au[l], Bu[l], Cu[l]).p1 : 0.f;
+      float q2_left = x1 ? hale_qv(gb[l], gf[l], gd[l], t, xi - 1, T, X, Al[l], Bl[l], Cl[l]).p2 : 0.f;
+      const float s0 = -(dT(q1_up, qq.p1, t, T) + dT(q2_left, qq.p2, xi, X));
+      // (t,y) section: q at (t,y), q1 at (t-1,y), q2 at (t,y-1)
+      const int j = y0 + l;
+      qq = hale_qv(ha[l + 2], ha[l + 1], hb[l + 1], t, j, T, Y, P[l + 1], Q[l + 1], R[l + 1]);
+      q1_up = t1 ? hale_qv(hb[l + 1], hb[l], hc[l], t - 1, j, T, Y, Pu[l], Qu[l], Ru[l]).p1 : 0.f;
+      q2_left = j >= 1 ? hale_qv(ha[l + 1], ha[l], hb[l], t, j - 1, T, Y, P[l], Q[l], R[l]).p2 : 0.f;
+      const float s1 = -(dT(q1_up, qq.p1, t, T) + dT(q2_left, qq.p2, j, Y));
+      out[l] = s0 + s1;
+    }
+    st_row<V>(xo, o, out);
   }
 }
 
@@ -116,6 +264,27 @@ __global__ __launch_bounds__(256) void structure_tensor_kernel(const float* __re
     gvv[idx] = gv * gv;
     gvh[idx] = gv * gh;
     ghh[idx] = gh * gh;
+  }
+}
+// the same forward-difference gradients along t, x and y of a [C][T][X][Y] patch, and the five products of the (t,x) and (t,y)
+// section tensors in one pass (gtt is shared by both families)
+__global__ __launch_bounds__(256) void structure_tensor_sections_kernel(const float* __restrict__ x, size_t total, int T, int X, int Y, float dt,
+                                                                        float dx, float dy, float* __restrict__ gtt, float* __restrict__ gtx,
+                                                                        float* __restrict__ gxx, float* __restrict__ gty, float* __restrict__ gyy) {
+  const size_t sv = (size_t)X * Y;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int yi = (int)(idx % (size_t)Y);
+    const size_t r = idx / (size_t)Y;
+    const int xi = (int)(r % (size_t)X), t = (int)(r / (size_t)X % (size_t)T);
+    const float x0 = x[idx];
+    const float gt = t <= T - 2 ? (x[idx + sv] - x0) / dt : 0.f;
+    const float gx = xi <= X - 2 ? (x[idx + Y] - x0) / dx : 0.f;
+    const float gy = yi <= Y - 2 ? (x[idx + 1] - x0) / dy : 0.f;
+    gtt[idx] = gt * gt;
+    gtx[idx] = gt * gx;
+    gxx[idx] = gx * gx;
+    gty[idx] = gt * gy;
+    gyy[idx] = gy * gy;
   }
 }
 // eigen-decomposition of the 2x2 tensor per sample: phi = atan((l1 - gvv) / gvh) with NaN -> 0 (0/0 where the tensor is
@@ -190,6 +359,32 @@ extern "C" int dpi_hale2d(const float* x, const float* a, const float* b, const 
   if (adjoint) hale2d_adj_kernel<<<op_blocks(total), 256, 0, (hipStream_t)stream>>>(x, a, b, c, total, H, W, y);
   else hale2d_fwd_kernel<<<op_blocks(total), 256, 0, (hipStream_t)stream>>>(x, a, b, c, total, H, W, y);
   return dpi_check_launch("hale2d");
+}
+
+extern "C" int dpi_hale_sections(const float* x, const float* coef, int C, int T, int X, int Y, int adjoint, float* y, void* stream) {
+  DPI_REQUIRE(x && coef && y && x != y && C > 0 && T > 0 && X > 0 && Y > 0, "hale_sections: bad argument");
+  const size_t rows = (size_t)C * T * X, n = rows * Y;
+  DPI_REQUIRE(n < ((size_t)1 << 31), "hale_sections: patch of %zu samples exceeds 2^31", n);
+  const bool v4 = Y % 4 == 0 && ((uintptr_t)x | (uintptr_t)coef | (uintptr_t)y) % 16 == 0;
+  const unsigned nb = op_blocks(v4 ? n / 4 : n);
+  hipStream_t st = (hipStream_t)stream;
+  if (adjoint) {
+    if (v4) hale_sections_adj_kernel<4><<<nb, 256, 0, st>>>(x, coef, (unsigned)rows, T, X, Y, n, y);
+    else hale_sections_adj_kernel<1><<<nb, 256, 0, st>>>(x, coef, (unsigned)rows, T, X, Y, n, y);
+  } else {
+    if (v4) hale_sections_fwd_kernel<4><<<nb, 256, 0, st>>>(x, coef, (unsigned)rows, T, X, Y, n, y);
+    else hale_sections_fwd_kernel<1><<<nb, 256, 0, st>>>(x, coef, (unsigned)rows, T, X, Y, n, y);
+  }
+  return dpi_check_launch("hale_sections");
+}
+
+extern "C" int dpi_structure_tensor_sections(const float* x, int C, int T, int X, int Y, float dt, float dx, float dy, float* gtt, float* gtx,
+                                             float* gxx, float* gty, float* gyy, void* stream) {
+  DPI_REQUIRE(x && gtt && gtx && gxx && gty && gyy && C > 0 && T > 0 && X > 0 && Y > 0 && dt != 0.f && dx != 0.f && dy != 0.f,
+              "structure_tensor_sections: bad argument");
+  const size_t total = (size_t)C * T * X * Y;
+  structure_tensor_sections_kernel<<<op_blocks(total), 256, 0, (hipStream_t)stream>>>(x, total, T, X, Y, dt, dx, dy, gtt, gtx, gxx, gty, gyy);
+  return dpi_check_launch("structure_tensor_sections");
 }
 
 extern "C" int dpi_structure_tensor(const float* x, size_t N, int H, int W, float dv, float dh, float* gvv, float* gvh, float* ghh, void* stream) {

@@ -289,24 +289,32 @@ class Interpolator:
         return self.optimizer._params if (ops._deferred and self.optimizer is not None) else None
 
     def regularization(self, out_, main_loss):
-        """Extra loss term hook.  The base path has none.  With --aa_weight > 0 (2-D / 2.5-D sections) the anti-aliasing add-on
-        is active: aa_weight * loss_fn(Hale2D(dips)(out), 0) — the directional Laplacian of utils/slopes.py along dips estimated
-        once per patch from the Gaussian-smoothed structure tensor of the decimated data (build_regularizer)."""
+        """Extra loss term hook.  The base path has none.  With --aa_weight > 0 the anti-aliasing add-on is active:
+        aa_weight * loss_fn(Hale2D(dips)(out), 0) on 2-D / 2.5-D sections — the directional Laplacian of utils/slopes.py along dips
+        estimated once per patch from the Gaussian-smoothed structure tensor of the decimated data (build_regularizer) — and
+        aa_weight * (loss_fn(L_tx out, 0) + loss_fn(L_ty out, 0)) on 3-D patches, the same operator on the (t,x) and the (t,y)
+        sections (Hale2DSections)."""
         if getattr(self, "_aa_op", None) is None:
             return None
         lap = self._aa_op(out_)
         reg_loss, _ = ops.masked_loss(lap, self._aa_zero, self._aa_one, self.loss_kind)
+        if lap.ndim == out_.ndim + 1:
+            # one loss pass over [L_tx out, L_ty out]: both halves have C*T*X*Y samples, so the sum of their two means is twice the mean
+            reg_loss = 2.0 * reg_loss
         return float(self.args.aa_weight), reg_loss
 
     def build_regularizer(self):
         """Anti-aliasing add-on (BASELINE configs[3]; the reference ships the operators — utils/slopes.py, operators/ — but no
-        caller): dips from the structure tensor of the available traces, smoothed with --aa_smooth."""
+        caller): dips from the structure tensor of the available traces, smoothed with --aa_smooth.  On a 3-D patch
+        (1,C,T,X,Y) the 2-D add-on runs on both families of vertical sections, (t,x) and (t,y), each with its own dip field;
+        --aa_dips then holds 2*C*T*X*Y values, the (t,x) dips first."""
         self._aa_op = None
         a = self.args
         if not getattr(a, "aa_weight", 0.0):
             return
-        if self.img_.ndim != 4:
-            raise NotImplementedError("the anti-aliasing add-on works on 2-D / 2.5-D sections (BCHW)")
+        if self.img_.ndim == 5:
+            self._build_regularizer_sections()
+            return
         if a.aa_dips is not None:
             dips = torch.from_numpy(np.load(a.aa_dips).astype(np.float32)).to(self.device).reshape(self.img_.shape)
         else:
@@ -314,6 +322,22 @@ class Interpolator:
         self._aa_op = u.Hale2D(dips)
         self._aa_zero = torch.zeros_like(self.img_)
         self._aa_one = torch.ones_like(self.img_)
+        self.history = u.HistoryReg(a.epochs)
+
+    def _build_regularizer_sections(self):
+        a = self.args
+        if a.aa_dips is not None:
+            d = np.load(a.aa_dips)
+            if d.size != 2 * self.img_.numel():
+                raise ValueError("--aa_dips %s holds %d values; a 3-D patch of shape %s needs 2*C*T*X*Y = %d (the (t,x) dips, then the "
+                                 "(t,y) dips)" % (a.aa_dips, d.size, tuple(self.img_.shape[1:]), 2 * self.img_.numel()))
+            dips = torch.from_numpy(d.astype(np.float32)).to(self.device).reshape((2,) + tuple(self.img_.shape))
+            phi_tx, phi_ty = dips[0], dips[1]
+        else:
+            phi_tx, phi_ty = u.structure_tensor_dips_sections(self.img_ * self.mask_, smooth=float(a.aa_smooth))
+        self._aa_op = u.Hale2DSections(phi_tx, phi_ty)
+        self._aa_zero = torch.zeros((2,) + tuple(self.img_.shape), dtype=torch.float32, device=self.device)
+        self._aa_one = torch.ones((2,) + tuple(self.img_.shape), dtype=torch.float32, device=self.device)
         self.history = u.HistoryReg(a.epochs)
 
     def optimize(self, net_inputs=None, verbose=True, mode="auto", check_every=64):

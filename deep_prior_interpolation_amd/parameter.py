@@ -84,9 +84,11 @@ _FLAGS = [
                                "with LeakyReLU and no dropout (the fused nodes); 2-D / 2.5-D nets, Skip3D, UNet, ELU / dropout nets and runs with "
                                "--data_forgetting_factor keep fp32 tensors under --precision bf16 (operand rounding only, as bf16mm)")),
     # anti-aliasing add-on (ours: the reference ships operators/ + utils/slopes.py without a caller)
-    (("--aa_weight",), dict(type=float, required=False, default=0.0, help="Weight of the directional-Laplacian regulariser (0 = off)")),
+    (("--aa_weight",), dict(type=float, required=False, default=0.0, help="Weight of the directional-Laplacian regulariser (0 = off); "
+                                                                          "on 3-D patches it acts on the (t,x) and the (t,y) sections")),
     (("--aa_smooth",), dict(type=float, required=False, default=2.0, help="Gaussian smoothing (std, samples) of the structure tensor")),
-    (("--aa_dips",), dict(type=str, required=False, help="Optional .npy with a precomputed dip field (same shape as a section)")),
+    (("--aa_dips",), dict(type=str, required=False, help="Optional .npy with a precomputed dip field (same shape as a section; "
+                                                         "3-D: 2*C*T*X*Y values, the (t,x) dips then the (t,y) dips)")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),

@@ -43,7 +43,8 @@ extern "C" {
 #define DPI_CHAIN_STRIDE 5
 
 const char* dpi_last_error(void);
-/* ABI version (404 = round 6: the ten dpi_set_* tuning functions left the ABI for dpi_set_option): 300 = round 3 (dpi_conv_desc carries its own size as first field), 301 adds dpi_conv_fwd_ws / dpi_conv_bwd_data_ws /
+/* ABI version (405 = dpi_hale_sections / dpi_structure_tensor_sections: the anti-aliasing add-on on 3-D patches; 404 = round 6: the ten
+ * dpi_set_* tuning functions left the ABI for dpi_set_option): 300 = round 3 (dpi_conv_desc carries its own size as first field), 301 adds dpi_conv_fwd_ws / dpi_conv_bwd_data_ws /
  * dpi_conv_bwd_data_dual, 401 = dpi_pack_scratch_bytes / dpi_pack_release, 402 = dpi_pack_forget (round 5), 403 = dpi_join_bwd (round 5), 400 = round 4: dpi_conv_desc grows the `io` field (bf16 storage of activations) and the elementwise entry
  * points get `_io` twins that take the storage types of their tensors.  A binding checks `>=` the version it was written against and
  * dpi_conv_desc_size() == its own struct size. */
@@ -377,6 +378,16 @@ int dpi_hale2d(const float* x, const float* a, const float* b, const float* c, s
 int dpi_structure_tensor(const float* x, size_t N, int H, int W, float dv, float dh, float* gvv, float* gvh, float* ghh,
                          void* stream);
 int dpi_dips(const float* gvv, const float* gvh, const float* ghh, size_t n, float* phi, float* anisotropy, void* stream);
+/* ABI 405.  The same operator on both families of vertical sections of a [C][T][X][Y] patch (Y contiguous): the (t,x) sections
+ * (v = t, h = x) and the (t,y) sections (v = t, h = y).  coef: six [C][T][X][Y] fields a, b, c of the (t,x) family, then of the (t,y)
+ * family.  Forward: y = [2][C][T][X][Y], the (t,x) result then the (t,y) result.  Adjoint: x is that [2][...] tensor and
+ * y = L_tx^T x[0] + L_ty^T x[1].  Per sample the same arithmetic as dpi_hale2d on the section.  C*T*X*Y < 2^31; x != y. */
+int dpi_hale_sections(const float* x, const float* coef, int C, int T, int X, int Y, int adjoint, float* y, void* stream);
+/* ABI 405.  dpi_structure_tensor for both section families of a [C][T][X][Y] patch in one pass: forward-difference gradients gt, gx,
+ * gy (spacings dt, dx, dy) and the five products gtt (shared), gtx, gxx (t,x) and gty, gyy (t,y).  The smoothing is dpi_fir_axis0
+ * along the two axes of each family, the angles dpi_dips. */
+int dpi_structure_tensor_sections(const float* x, int C, int T, int X, int Y, float dt, float dx, float dy, float* gtt, float* gtx,
+                                  float* gxx, float* gty, float* gyy, void* stream);
 
 /* ---------------------------------------------------------------- POCS regulariser --------------
  * Replaces utils/pocs.py:5-19 (threshold / compute_threshold: out = max(x) * scale with scale = perc/100, kept on the device;
