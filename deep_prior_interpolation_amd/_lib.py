@@ -15,7 +15,7 @@ class DpiError(RuntimeError):
     pass
 
 
-ABI_VERSION = 405      # dpi_hale_sections / dpi_structure_tensor_sections (405); dpi_set_option replaces the ten dpi_set_* tuning exports (404); include/dpi_hip.h: dpi_conv_desc starts with its own size (300); dpi_conv_fwd_ws / dpi_conv_bwd_data_ws (301); `io` + the *_io entry points (400); dpi_pack_* (401); dpi_pack_forget (402); dpi_join_bwd (403)
+ABI_VERSION = 406      # dpi_masked_loss_holdout / dpi_loop_control_holdout (406); dpi_hale_sections / dpi_structure_tensor_sections (405); dpi_set_option replaces the ten dpi_set_* tuning exports (404); include/dpi_hip.h: dpi_conv_desc starts with its own size (300); dpi_conv_fwd_ws / dpi_conv_bwd_data_ws (301); `io` + the *_io entry points (400); dpi_pack_* (401); dpi_pack_forget (402); dpi_join_bwd (403)
 
 # dpi_conv_desc.io bits / the `io` masks of the *_io entry points (bf16 storage of activations, BASELINE configs[4])
 IO_X_BF16, IO_Y_BF16, IO_DY_BF16, IO_DX_BF16 = 1, 2, 4, 8
@@ -90,6 +90,8 @@ SIGNATURES = {
     "dpi_adam_multi": (_I, [_P, _P, _I, _P, C.c_double, C.c_double, C.c_double, _P, _P]),
     "dpi_loop_control": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, C.c_double, C.c_double, _I, C.c_double, _P]),
     "dpi_copy_if": (_I, [_P, _P, _P, _Z, _P]),
+    "dpi_masked_loss_holdout": (_I, [_P, _P, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P]),     # ABI 406: --holdout
+    "dpi_loop_control_holdout": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, C.c_double, C.c_double, _I, C.c_double, _P]),
     "dpi_noise_add": (_I, [_P, _Z, _F, _U64, _P, _P, _P]),
     "dpi_fill_normal": (_I, [_P, _Z, _F, _F, _U64, _U64, _P]),
     "dpi_fir_axis0": (_I, [_P, _P, _I, _I, _I, _Z, _P, _P]),

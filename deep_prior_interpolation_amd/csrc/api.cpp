@@ -22,7 +22,7 @@ int dpi_check_launch(const char* what) {
 }
 
 extern "C" const char* dpi_last_error(void) { return g_err; }
-extern "C" int dpi_version(void) { return 405; }
+extern "C" int dpi_version(void) { return 406; }
 extern "C" int dpi_conv_desc_size(void) { return (int)sizeof(dpi_conv_desc); }
 
 extern "C" int dpi_device_info(int device, int* cus, int* lds_bytes, size_t* hbm_bytes, char* name, int name_len) {

@@ -50,6 +50,70 @@ __global__ __launch_bounds__(64) void loss_final_kernel(const double* __restrict
   }
 }
 
+// ---- masked loss with held-out traces (--holdout) ------------------------------------------------------------------
+// The walk, the grid and the first seven sums of loss_partial_kernel with m_tr = m * (1 - h) in place of m, so that the training part is
+// bit for bit dpi_masked_loss on a materialised m_tr; the same pass adds the misfit on m_ho = m * h.  h is one float per trace
+// (sel[c * S + s] of the layout [C][T][S]); its index follows i incrementally, no division inside the loop.
+// partial layout per block (stride 16): {the seven sums of loss_partial_kernel, unused, sum |e| or e^2 on m_ho, sum (t m_ho)^2,
+// sum (e m_ho)^2, number of held samples} with e = t - o
+__global__ __launch_bounds__(256) void loss_holdout_partial_kernel(const float* __restrict__ out, const float* __restrict__ img,
+                                                                   const float* __restrict__ mask, const float* __restrict__ sel,
+                                                                   uint32_t TS, uint32_t S, size_t n, int kind, float gscale,
+                                                                   float* __restrict__ dout, double* __restrict__ ws) {
+  double acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const float inv_n = gscale / (float)n;
+  const size_t G = (size_t)gridDim.x * 256;
+  const uint32_t Gc = (uint32_t)(G / TS), Gr = (uint32_t)(G % TS), Gs = (uint32_t)(G % S);
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t c = (uint32_t)(i / TS), r = (uint32_t)(i % TS), s = (uint32_t)(i % S);      // i = c * TS + r, s = i mod S (n < 2^32)
+  for (; i < n; i += G) {
+    const float o = out[i], t = img[i], m0 = mask[i], h = sel[(size_t)c * S + s];
+    const float m = m0 * (1.f - h);
+    const float d = o * m - t * m;
+    float g;
+    if (kind == 1) { acc[0] += (double)d * d; g = 2.f * d * m * inv_n; }
+    else { acc[0] += fabsf(d); g = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * m * inv_n; }
+    if (dout) dout[i] = g;
+    const float e = t - o;
+    acc[1] += (double)t * t; acc[2] += (double)e * e; acc[3] += o; acc[4] += t;
+    acc[5] += (double)o * o; acc[6] += (double)o * t;
+    const float mh = m0 * h;
+    const float eh = e * mh, th = t * mh;
+    acc[7] += kind == 1 ? (double)eh * eh : (double)fabsf(eh);
+    acc[8] += (double)th * th; acc[9] += (double)eh * eh; acc[10] += mh != 0.f ? 1.0 : 0.0;
+    c += Gc; r += Gr; s += Gs;
+    if (r >= TS) { r -= TS; ++c; }
+    if (s >= S) s -= S;
+  }
+  __shared__ double sh[4];
+#pragma unroll
+  for (int k = 0; k < 11; ++k) {
+    const double v = block_sum(acc[k], sh);
+    if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 16 + (k < 7 ? k : k + 1)] = v;
+  }
+}
+
+__global__ __launch_bounds__(64) void loss_holdout_final_kernel(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
+  double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = threadIdx.x; b < nblk; b += 64) {          // per k the order of loss_final_kernel; the 12 loads of a row issue together
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+      if (k != 7) acc[k] += ws[(size_t)b * 16 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = wave_sum(acc[k]);
+  if (threadIdx.x == 0) {                                  // res[0..7] exactly as loss_final_kernel
+    const double loss = acc[0] / n;
+    const double snr = 10.0 * log10(acc[1] / acc[2]);
+    const double mo = acc[3] / n, mt = acc[4] / n;
+    const double cov = acc[6] - n * mo * mt;
+    const double vt = acc[1] - n * mt * mt, vo = acc[5] - n * mo * mo;
+    res[0] = loss; res[1] = snr; res[2] = cov / (sqrt(vt) * sqrt(vo));
+    res[3] = acc[1]; res[4] = acc[2]; res[5] = acc[3]; res[6] = acc[4]; res[7] = acc[5];
+    res[8] = acc[8] / acc[11]; res[9] = 10.0 * log10(acc[9] / acc[10]); res[10] = acc[11];
+  }
+}
+
 // ---- Adam -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adam_kernel(const dpi_adam_tensor* __restrict__ tensors, const int64_t* __restrict__ sizes,
                                                    const float* __restrict__ step_lr, double beta1d, double beta2d, double epsd,
@@ -203,6 +267,46 @@ __global__ void loop_control_kernel(const double* __restrict__ metrics, double* 
   state[0] = (double)(it + 1);
 }
 
+// The same with a held-out part (--holdout): metrics = the 11 doubles of dpi_masked_loss_holdout; history rows of six
+// {loss, snr, pcorr, lr, val_loss, val_snr}; out_best and early stopping follow val_loss, ReduceLROnPlateau the training loss.
+// state (double[10]): {iter, loss_min, plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved, val_min, best_iter}
+__global__ void loop_control_holdout_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist,
+                                            int max_iters, float* __restrict__ step_lr, int* __restrict__ active, int* __restrict__ improved,
+                                            int use_plateau, double factor, double threshold, int patience, double min_lr, double lr_eps,
+                                            int es_patience, double es_min_delta) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  *improved = 0;
+  if (!*active) return;
+  const int it = (int)state[0];
+  const double loss = metrics[0], val = metrics[8];
+  const double lr = (double)step_lr[1];
+  if (it < max_iters) {
+    double* row = hist + 6 * (size_t)it;
+    row[0] = loss; row[1] = metrics[1]; row[2] = metrics[2]; row[3] = lr; row[4] = val; row[5] = metrics[9];
+  }
+  if (it == 0 || loss <= state[1]) state[1] = loss;
+  if (it == 0 || val <= state[8]) { state[8] = val; state[9] = (double)it; *improved = 1; }
+  if (use_plateau) {
+    if (loss < state[2] * (1.0 - threshold)) { state[2] = loss; state[3] = 0.0; }
+    else state[3] += 1.0;
+    if (state[3] > (double)patience) {
+      const double nl = fmax(lr * factor, min_lr);
+      if (lr - nl > lr_eps) step_lr[1] = (float)nl;
+      state[3] = 0.0;
+    }
+  }
+  if (es_patience != 0) {
+    if (state[6] == 0.0) { state[4] = val; state[6] = 1.0; }
+    else if (val != val) *active = 0;
+    else {
+      if (val < state[4] - state[4] * es_min_delta / 100.0) { state[5] = 0.0; state[4] = val; }
+      else state[5] += 1.0;
+      if (state[5] >= (double)es_patience) *active = 0;
+    }
+  }
+  state[0] = (double)(it + 1);
+}
+
 __global__ __launch_bounds__(256) void copy_if_kernel(const int* __restrict__ flag, const float* __restrict__ src, float* __restrict__ dst,
                                                       size_t n) {
   if (*flag == 0) return;
@@ -231,6 +335,23 @@ extern "C" int dpi_masked_loss(const float* out, const float* img, const float* 
   if (int e = dpi_check_launch("loss_partial")) return e;
   loss_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>(ws, (int)nb, (double)n, result);
   return dpi_check_launch("loss_final");
+}
+
+extern "C" int dpi_masked_loss_holdout(const float* out, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
+                                       int kind, float grad_scale, float* dout, double* ws, double* result, void* stream) {
+  DPI_REQUIRE(out && img && mask && sel && ws && result && C > 0 && T > 0 && S > 0, "masked_loss_holdout: bad argument");
+  DPI_REQUIRE(kind == 0 || kind == 1, "masked_loss_holdout: kind must be 0 (L1) or 1 (MSE)");
+  const size_t n = (size_t)C * T * S;
+  // the trace index is 32-bit: r + (G mod TS) < TS + G and s + (G mod S) < S + G must not wrap, G = grid * 256 <= kLossBlocks * 256
+  DPI_REQUIRE(n <= (size_t)0xFFFFFFFFu - (size_t)kLossBlocks * 256, "masked_loss_holdout: %zu samples: the trace index is 32-bit", n);
+  size_t nb = cdivz(n, 256 * 8);                           // the grid of dpi_masked_loss
+  if (nb > kLossBlocks) nb = kLossBlocks;
+  if (nb < 1) nb = 1;
+  loss_holdout_partial_kernel<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(out, img, mask, sel, (uint32_t)((size_t)T * S), (uint32_t)S, n, kind,
+                                                                             grad_scale, dout, ws);
+  if (int e = dpi_check_launch("loss_holdout_partial")) return e;
+  loss_holdout_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>(ws, (int)nb, (double)n, result);
+  return dpi_check_launch("loss_holdout_final");
 }
 
 extern "C" int dpi_adam_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors, const float* step_lr,
@@ -289,6 +410,15 @@ extern "C" int dpi_loop_control(const double* metrics, double* state, double* hi
   loop_control_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, use_plateau, factor,
                                                         threshold, patience, min_lr, lr_eps, es_patience, es_min_delta);
   return dpi_check_launch("loop_control");
+}
+
+extern "C" int dpi_loop_control_holdout(const double* metrics, double* state, double* hist, int max_iters, float* step_lr, int* active,
+                                        int* improved, int use_plateau, double factor, double threshold, int patience, double min_lr,
+                                        double lr_eps, int es_patience, double es_min_delta, void* stream) {
+  DPI_REQUIRE(metrics && state && hist && step_lr && active && improved && max_iters > 0, "loop_control_holdout: bad argument");
+  loop_control_holdout_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, use_plateau,
+                                                                factor, threshold, patience, min_lr, lr_eps, es_patience, es_min_delta);
+  return dpi_check_launch("loop_control_holdout");
 }
 
 extern "C" int dpi_copy_if(const int* flag, const float* src, float* dst, size_t n, void* stream) {

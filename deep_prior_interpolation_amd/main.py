@@ -36,7 +36,12 @@ class Interpolator:
         self.iter_to_be_saved = list(range(0, args.epochs, int(args.save_every))) if args.save_every is not None else [0]
         self.loss_min = None
         self.outchannel = args.imgchannel
-        self.history = u.History(args.epochs)
+        self.holdout = float(getattr(args, "holdout", 0.0))      # --holdout (ours); Namespaces of reference args.txt files lack the key
+        if not 0.0 <= self.holdout <= 0.5:
+            raise ValueError("--holdout must lie in [0, 0.5], got %r" % self.holdout)
+        self.holdout_sel = self._holdout_dev = None              # per-trace selection: numpy (patch order without t) / device (C, S...)
+        self.best_iter = self.val_min = None
+        self.history = self._new_history()
         self.image_name = None
         self.img = self.img_ = self.mask = self.mask_ = None
         self.out_best = None
@@ -64,6 +69,7 @@ class Interpolator:
         self.noise_seed = seed
         self._patches_seen = 0
         self._noise_step.zero_()
+        self.holdout_sel = self._holdout_dev = None              # drawn again from the new seed (build_holdout)
 
     def load_data(self, data):
         """(T,X,Y,C) numpy patch -> (1,C,T,X,Y) fp32 device tensors; returns std of the masked data (main.py:118-139)."""
@@ -76,7 +82,32 @@ class Interpolator:
         to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.transpose(a, perm))).unsqueeze(0).float().to(self.device)
         self.img_ = to_dev(self.img)
         self.mask_ = to_dev(self.mask)
+        self.holdout_sel = self._holdout_dev = None
         return torch.std(self.img_ * self.mask_).item()
+
+    def build_holdout(self):
+        """--holdout: draw the per-trace split of the loaded patch from the patch seed (begin_patch) and upload it once.  optimize() and
+        graph_prepare() call it when the patch has none yet.  The selection lives in self.holdout_sel (numpy order (X[, Y], C)) and, as
+        the (C, S...) float 0/1 tensor the loss pass reads, in self._holdout_dev."""
+        if self.holdout <= 0.0:
+            return
+        self.holdout_sel = u.holdout_traces(self.mask, self.holdout, self.noise_seed, name=self.image_name)
+        dev = np.moveaxis(self.holdout_sel, -1, 0)                # (C, X[, Y]): the trace index (c, s) of the device layout (1, C, T, S...)
+        self._holdout_dev = torch.from_numpy(np.ascontiguousarray(dev)).to(self.device)
+
+    def _ensure_holdout(self):
+        if self.holdout > 0.0 and self._holdout_dev is None:
+            self.build_holdout()
+
+    def training_mask(self):
+        """The mask of the samples the network may see: mask_ itself without --holdout, else m_tr = mask_ * (1 - h) (drawn here if the patch
+        has no split yet).  Everything built from the data once per patch — the data-forgetting term of the input, the dips of the
+        anti-aliasing add-on — takes it, so no held-out sample reaches the network other than through the misfit it is measured by."""
+        self._ensure_holdout()
+        if self._holdout_dev is None:
+            return self.mask_
+        h = self._holdout_dev.reshape((1, self.mask_.shape[1], 1) + tuple(self.mask_.shape[3:]))
+        return self.mask_ * (1 - h)
 
     def release_packed_weights(self):
         """Hand the packed-weight scratch slots of this Interpolator's network back to the library (dpi_pack_forget, ABI 402): the bf16
@@ -139,7 +170,7 @@ class Interpolator:
             z = u.LowPassButterworth(fc=a.lowpass_fc, ndim=z.ndim - 2, fs=a.lowpass_fs, ntaps=a.lowpass_ntaps, order=4,
                                      nfft=2 ** u.nextpow2(z.shape[2]))(z)
         if a.data_forgetting_factor != 0:                       # main.py:86-97
-            data_ = self.img_ * self.mask_
+            data_ = self.img_ * self.training_mask()
             rep = int(np.ceil(z.shape[1] / data_.shape[1]))
             data_ = data_.repeat([1, rep] + [1] * (z.ndim - 2))[:, :a.inputdepth].contiguous()
             data_ = data_ * (torch.std(z) / torch.std(data_))
@@ -259,25 +290,41 @@ class Interpolator:
                                             _lib.ptr(input_), _lib.stream()), "dpi_axpy")
             self.input_list.append(u.torch_to_np(input_, True))
         out_ = self.net(input_)
-        total_loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, self.loss_kind)
+        if self._holdout_dev is None:
+            total_loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, self.loss_kind)
+        else:
+            total_loss, metrics = ops.masked_loss_holdout(out_, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
         reg = self.regularization(out_, total_loss)          # None, or (weight tensor / float, reg loss) of a subclass / add-on
         if reg is None:
             total_loss.backward()
             ops.finish_backward(self._grad_params())
-            l, s, p = metrics[:3].tolist()          # one read-back for loss, snr, pcorr
+            m = metrics[:10].tolist() if self._holdout_dev is not None else metrics[:3].tolist()       # one read-back
+            l, s, p = m[:3]
             self.history.append((l, s, p))
         else:
             eps, reg_loss = reg
             total = total_loss + eps * reg_loss
             total.backward()
             ops.finish_backward(self._grad_params())
-            main_l, s, p = metrics[:3].tolist()
+            m = metrics[:10].tolist() if self._holdout_dev is not None else metrics[:3].tolist()
+            main_l, s, p = m[:3]
             l, r = float(total.item()), float(reg_loss.item())
             self.history.append((l, main_l, r, s, p))           # HistoryReg layout (main_pocs.py:198-202)
         self.history.lr.append(self.optimizer.param_groups[0]["lr"])
-        if self.iiter == 0 or l <= self.loss_min:
-            self.loss_min = l
-            self._out_best_dev = out_.detach()   # stays on the GPU; copied to the host once, after the loop
+        if self._holdout_dev is None:
+            if self.iiter == 0 or l <= self.loss_min:
+                self.loss_min = l
+                self._out_best_dev = out_.detach()   # stays on the GPU; copied to the host once, after the loop
+        else:
+            # --holdout: out_best follows the misfit on the held-out traces (the later iterate wins a tie, as main.py:173-180 does on loss)
+            val, vsnr = m[8], m[9]
+            self.history.append_val(val, vsnr)
+            if self.iiter == 0 or l <= self.loss_min:
+                self.loss_min = l
+            if self.iiter == 0 or val <= self.val_min:
+                self.val_min, self.best_iter = val, self.iiter
+                self._out_best_dev = out_.detach()
+            self._last_val = val
         if self.iiter in self.iter_to_be_saved and self.iiter != 0:
             np.save(os.path.join(self.outpath, self.image_name.split(".")[0]
                                  + "_output%s.npy" % str(self.iiter).zfill(self.zfill)), self._to_numpy_out(out_))
@@ -318,11 +365,11 @@ class Interpolator:
         if a.aa_dips is not None:
             dips = torch.from_numpy(np.load(a.aa_dips).astype(np.float32)).to(self.device).reshape(self.img_.shape)
         else:
-            dips, _ = u.structure_tensor_dips(self.img_ * self.mask_, smooth=float(a.aa_smooth))
+            dips, _ = u.structure_tensor_dips(self.img_ * self.training_mask(), smooth=float(a.aa_smooth))
         self._aa_op = u.Hale2D(dips)
         self._aa_zero = torch.zeros_like(self.img_)
         self._aa_one = torch.ones_like(self.img_)
-        self.history = u.HistoryReg(a.epochs)
+        self.history = self._new_history()
 
     def _build_regularizer_sections(self):
         a = self.args
@@ -334,11 +381,11 @@ class Interpolator:
             dips = torch.from_numpy(d.astype(np.float32)).to(self.device).reshape((2,) + tuple(self.img_.shape))
             phi_tx, phi_ty = dips[0], dips[1]
         else:
-            phi_tx, phi_ty = u.structure_tensor_dips_sections(self.img_ * self.mask_, smooth=float(a.aa_smooth))
+            phi_tx, phi_ty = u.structure_tensor_dips_sections(self.img_ * self.training_mask(), smooth=float(a.aa_smooth))
         self._aa_op = u.Hale2DSections(phi_tx, phi_ty)
         self._aa_zero = torch.zeros((2,) + tuple(self.img_.shape), dtype=torch.float32, device=self.device)
         self._aa_one = torch.ones((2,) + tuple(self.img_.shape), dtype=torch.float32, device=self.device)
-        self.history = u.HistoryReg(a.epochs)
+        self.history = self._new_history()
 
     def optimize(self, net_inputs=None, verbose=True, mode="auto", check_every=64):
         """Adam loop with optional ReduceLROnPlateau and EarlyStopping (main.py:195-220).
@@ -348,8 +395,10 @@ class Interpolator:
         tracking, plateau LR and early stopping live on the device (dpi_loop_control / dpi_copy_if), the host only polls
         the `active` flag every `check_every` replays.  Same arithmetic, same stopping iteration.
         "auto" picks "graph" unless per-iteration host work was requested (net_inputs, --save_every) or the patch has >= 2^20 voxels
-        (eager with the weight-gradient and branch streams)."""
+        (eager with the weight-gradient and branch streams).
+        --holdout: out_best and early stopping follow the misfit on the held-out traces, ReduceLROnPlateau the training loss."""
         a = self.args
+        self._ensure_holdout()
         big = self.wants_weight_grad_overlap()
         if mode == "auto":
             # big fp32 patches are GPU-bound either way and gain from overlapping the weight gradients (eager only);
@@ -379,13 +428,21 @@ class Interpolator:
                     sched.step(loss)
                 if verbose:
                     print(self.history.log_message(self.iiter - 1), "\r", end="")
-                if stopper.step(loss):
+                if stopper.step(loss if self._holdout_dev is None else self._last_val):
                     break
             torch.cuda.synchronize(self.device)
             self.out_best = self._to_numpy_out(self._out_best_dev)
         self.elapsed = time() - start
         if verbose:
             print("\n" + u.sec2time(self.elapsed))
+            if self._holdout_dev is not None:
+                print("held-out SNR %+.2f dB at iteration %d (the selected output)" % (self.holdout_snr(), self.best_iter + 1))
+
+    def holdout_snr(self):
+        """val_snr of the selected output (iteration best_iter) of the last optimised patch; None without --holdout."""
+        if self.best_iter is None or not hasattr(self.history, "val_snr"):
+            return None
+        return float(self.history.val_snr[self.best_iter])
 
     # ---- hipGraph path -------------------------------------------------------------------------------------
     def graph_prepare(self, quiet_device=True):
@@ -407,9 +464,12 @@ class Interpolator:
             big = self.wants_weight_grad_overlap()
             ops.set_weight_grad_overlap(big, in_graph=big)
         opt = self.optimizer
-        self._g_state = torch.zeros(8, dtype=torch.float64, device=dev)
+        self._ensure_holdout()
+        ho = self._holdout_dev
+        cols = 4 if ho is None else 6                    # history row {loss, snr, pcorr, lr[, val_loss, val_snr]}
+        self._g_state = torch.zeros(8 if ho is None else 10, dtype=torch.float64, device=dev)
         self._g_state[2] = float("inf")
-        self._g_hist = torch.zeros(a.epochs * 4, dtype=torch.float64, device=dev)
+        self._g_hist = torch.zeros(a.epochs * cols, dtype=torch.float64, device=dev)
         self._g_improved = torch.zeros(1, dtype=torch.int32, device=dev)
         self._g_best = None
         kind = self.loss_kind
@@ -422,16 +482,20 @@ class Interpolator:
             ops.begin_iteration()
             opt.zero_grad()
             out_ = self.net(self.perturbed_input())
-            loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, kind)
+            if ho is None:
+                loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, kind)
+            else:
+                loss, metrics = ops.masked_loss_holdout(out_, self.img_, self.mask_, ho, kind)
             loss.backward()
             ops.finish_backward(self._grad_params())
             opt.step()                                   # skipped on the device once `active` is 0
             if self._g_best is None:
                 self._g_best = torch.empty_like(out_)
-            _lib.check(L.dpi_loop_control(_lib.ptr(metrics), _lib.ptr(self._g_state), _lib.ptr(self._g_hist), a.epochs,
-                                          _lib.ptr(opt.step_lr), _lib.ptr(opt.active), _lib.ptr(self._g_improved),
-                                          int(bool(a.reduce_lr)), float(a.lr_factor), float(a.lr_thresh), int(a.lr_patience), 0.0, 1e-8,
-                                          int(a.earlystop_patience), float(a.earlystop_min_delta), _lib.stream()), "dpi_loop_control")
+            control = L.dpi_loop_control if ho is None else L.dpi_loop_control_holdout
+            _lib.check(control(_lib.ptr(metrics), _lib.ptr(self._g_state), _lib.ptr(self._g_hist), a.epochs,
+                               _lib.ptr(opt.step_lr), _lib.ptr(opt.active), _lib.ptr(self._g_improved),
+                               int(bool(a.reduce_lr)), float(a.lr_factor), float(a.lr_thresh), int(a.lr_patience), 0.0, 1e-8,
+                               int(a.earlystop_patience), float(a.earlystop_min_delta), _lib.stream()), "dpi_loop_control")
             _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(out_), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
 
@@ -462,10 +526,14 @@ class Interpolator:
         else:
             torch.cuda.current_stream(self.device).synchronize()
         n = int(self._g_state[0].item())
-        h = self._g_hist[:4 * n].view(n, 4).cpu().numpy()
-        self.history = u.History(self.args.epochs)
+        cols = self._g_hist.numel() // self.args.epochs
+        h = self._g_hist[:cols * n].view(n, cols).cpu().numpy()
+        self.history = self._new_history()
         self.history.loss, self.history.snr, self.history.pcorr, self.history.lr = (h[:, i].tolist() for i in range(4))
         self.loss_min = float(self._g_state[1].item())
+        if cols == 6:
+            self.history.val_loss, self.history.val_snr = h[:, 4].tolist(), h[:, 5].tolist()
+            self.val_min, self.best_iter = float(self._g_state[8].item()), int(self._g_state[9].item())
         self.iiter = n
         self._out_best_dev = self._g_best
         self.out_best = self._to_numpy_out(self._g_best)
@@ -479,8 +547,12 @@ class Interpolator:
                     break
                 if verbose:
                     n = int(self._g_state[0].item())
-                    l, s_, p_ = self._g_hist[4 * (n - 1):4 * (n - 1) + 3].tolist()
-                    print("Iter %d, Loss = %+.2e, SNR = %+2.2f dB, PCORR = %+.2f %%" % (n, l, s_, p_ * 100), "\r", end="")
+                    cols = self._g_hist.numel() // self.args.epochs
+                    row = self._g_hist[cols * (n - 1):cols * n].tolist()
+                    msg = "Iter %d, Loss = %+.2e, SNR = %+2.2f dB, PCORR = %+.2f %%" % (n, row[0], row[1], row[2] * 100)
+                    if cols == 6:
+                        msg += ", VAL = %.2e, VSNR = %+.2f dB" % (row[4], row[5])
+                    print(msg, "\r", end="")
         self.graph_finish()
 
     def has_regularizer(self):
@@ -495,21 +567,30 @@ class Interpolator:
 
     # ------------------------------------------------------------------------------------------
     def save_result(self):
-        np.save(os.path.join(self.outpath, self.image_name + "_run.npy"), {
+        run = {
             "device": u.get_gpu_name(), "elapsed": u.sec2time(self.elapsed), "outpath": self.outpath,
             "history": self.history, "mask": self.mask, "image": self.img, "output": self.out_best,
             "noise": self.input_list,
-        })
+        }
+        if self.holdout > 0.0:
+            # the selection with a unit t axis, in the patch's numpy order (broadcasts against mask: m_ho = mask * holdout); None for a
+            # flat patch that was not optimised
+            run["holdout"] = None if self.holdout_sel is None else self.holdout_sel[None]
+            run["best_iter"] = self.best_iter
+        np.save(os.path.join(self.outpath, self.image_name + "_run.npy"), run)
         if self.args.savemodel:
             torch.save(self.net.state_dict(), os.path.join(self.outpath, self.image_name + "_model.pth"))
 
     def clean(self):
         self.iiter = 0
         self.loss_min = None
+        self.best_iter = self.val_min = None
         self._out_best_dev = None
         self.history = self._new_history()
 
     def _new_history(self):
+        if self.holdout > 0.0:
+            return u.HistoryRegHoldout(self.args.epochs) if self.has_regularizer() else u.HistoryHoldout(self.args.epochs)
         return u.HistoryReg(self.args.epochs) if self.has_regularizer() else u.History(self.args.epochs)
 
 

@@ -25,6 +25,9 @@ from .parameter import parse_arguments
 
 class Interpolator(_Base):
     def __init__(self, args, outpath, device=None, seed=0):
+        if getattr(args, "holdout", 0.0) > 0.0:
+            raise ValueError("main_pocs does not support --holdout (got %g): the POCS projection re-inserts every known trace into its "
+                             "target, held-out ones included; run main.py for self-validation" % args.holdout)
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

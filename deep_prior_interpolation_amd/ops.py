@@ -1419,6 +1419,36 @@ class MaskedLossFn(torch.autograd.Function):
         return dout * gloss, None, None, None
 
 
+class MaskedLossHoldoutFn(torch.autograd.Function):
+    """MaskedLossFn with held-out traces (--holdout): the loss, its gradient, SNR and PCORR on m_tr = mask * (1 - sel), and in the same
+    pass the misfit on the held-out samples m_ho = mask * sel.  out / img / mask: (1, C, T, S...); sel: (C, S...) 0/1 per trace.
+    Returns (loss, metrics) with metrics = device double[11] {the eight of MaskedLossFn, val_loss, val_snr, N_ho}."""
+
+    @staticmethod
+    def forward(ctx, out, img, mask, sel, kind):
+        out, img, mask, sel = _req(out, "loss output"), _req(img, "loss target"), _req(mask, "loss mask"), _req(sel, "holdout selection")
+        if not (out.shape == img.shape == mask.shape) or out.ndim < 4 or out.shape[0] != 1 \
+                or tuple(sel.shape) != (out.shape[1],) + tuple(out.shape[3:]):
+            raise _lib.DpiError("loss_holdout: shapes %s / %s / %s / selection %s: expected (1, C, T, S...) and (C, S...)"
+                                % (tuple(out.shape), tuple(img.shape), tuple(mask.shape), tuple(sel.shape)))
+        L = _lib.load()
+        C_, T_ = out.shape[1], out.shape[2]
+        S_ = out.numel() // (C_ * T_)
+        ws = torch.empty(2 * L.dpi_loss_ws_doubles(out.numel()), dtype=torch.float64, device=out.device)
+        res = torch.empty(11, dtype=torch.float64, device=out.device)
+        dout = torch.empty_like(out)
+        check(L.dpi_masked_loss_holdout(ptr(out), ptr(img), ptr(mask), ptr(sel), C_, T_, S_, int(kind), 1.0, ptr(dout), ptr(ws), ptr(res),
+                                        stream()), "dpi_masked_loss_holdout")
+        ctx.save_for_backward(dout)
+        ctx.mark_non_differentiable(res)
+        return res[0].to(torch.float32), res
+
+    @staticmethod
+    def backward(ctx, gloss, _gres):
+        (dout,) = ctx.saved_tensors
+        return dout * gloss, None, None, None, None
+
+
 class MaxPool2x2Fn(torch.autograd.Function):
     """nn.MaxPool2d(2, 2) on (1,C,H,W) (reference unet.py:42)."""
 
@@ -1553,3 +1583,7 @@ def concat_crop(xs):
 
 def masked_loss(out, img, mask, kind="mae"):
     return MaskedLossFn.apply(out, img, mask, 1 if kind == "mse" else 0)
+
+
+def masked_loss_holdout(out, img, mask, sel, kind="mae"):
+    return MaskedLossHoldoutFn.apply(out, img, mask, sel, 1 if kind == "mse" else 0)

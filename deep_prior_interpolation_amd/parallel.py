@@ -209,7 +209,7 @@ class _Replayer:
             raise self.error
 
 
-def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, check_every=64):
+def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, check_every=64, holdout_snrs=None):
     """K concurrency slots, each with its own Interpolator, stream and captured iteration graph, kept full from the shared queue: a slot
     that has finished its patch (overlap-add, result file) claims the next index and prepares it — weights, z, iteration 0, the graph
     capture: ~50 ms of host time alone, ~250 ms next to five running patches (tools/c3_setup_probe.py) — while a replay thread keeps the
@@ -229,6 +229,7 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
         acc.add(T._best_for_acc, origins[i])
         if save:
             T.save_result()
+        _record_holdout(T, holdout_snrs)
         T.clean()
         mine.append(i)
 
@@ -318,13 +319,28 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
     return mine, t_prep[0]
 
 
-def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None, conc=1, queue=None, save=True, timings=None):
+def _record_holdout(T, holdout_snrs):
+    """--holdout: the held-out SNR of the output T selected for its patch, for the driver's summary (flat, skipped patches have none)."""
+    v = T.holdout_snr()
+    if holdout_snrs is not None and v is not None:
+        holdout_snrs.append(v)
+
+
+def _print_holdout_summary(rank, holdout_snrs):
+    if holdout_snrs:
+        print("rank %d: held-out SNR of the selected outputs over %d patches: mean %+.2f dB, min %+.2f dB"
+              % (rank, len(holdout_snrs), float(np.mean(holdout_snrs)), float(np.min(holdout_snrs))))
+
+
+def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None, conc=1, queue=None, save=True, timings=None,
+                    holdout_snrs=None):
     """Deep-prior optimisation of every patch this rank pulls from `queue`, `conc` patches at a time on one GPU, overlap-added
     into a device accumulator; ONE all-reduce at the end; returns (reconstructed volume, indices processed here).
 
     conc > 1 (DPI_CONCURRENT_PATCHES): every patch of a group gets its own Interpolator, stream and captured iteration graph
     (main.optimize_concurrently).  Patches whose loop cannot run as a graph (--save_every, data forgetting, >= 2^20 voxels)
-    and flat patches are handled one by one.  save=False skips the per-patch result files (bench.py)."""
+    and flat patches are handled one by one.  save=False skips the per-patch result files (bench.py).  holdout_snrs (list, --holdout):
+    the held-out SNR of every optimised patch's selected output is appended to it."""
     from time import perf_counter
     from .main import Interpolator, optimize_concurrently
     cropped = u.in_content_cropped_shape(vol_shape, pe.dim, pe.stride)
@@ -341,7 +357,7 @@ def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None,
     t_setup = t_loop = t_prep_live = 0.0
     if len(Ts) > 1 and os.environ.get("DPI_ROLLING_SLOTS", "1") == "1":
         t0 = perf_counter()
-        mine, t_prep_live = _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device)
+        mine, t_prep_live = _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, holdout_snrs=holdout_snrs)
         t_loop = perf_counter() - t0
         queue = PatchQueue(0)          # drained: the group loop below has nothing left to claim
     while True:
@@ -386,6 +402,7 @@ def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None,
             acc.add(T._best_for_acc, origins[i])
             if save:
                 T.save_result()
+            _record_holdout(T, holdout_snrs)
             T.clean()
             mine.append(i)
         t_setup += t1 - t0 - t_solo
@@ -432,10 +449,11 @@ def main(argv=None):
     origins = u.window_origins(vol.shape, pe.dim, pe.stride)
     conc = int(os.environ.get("DPI_CONCURRENT_PATCHES", "1"))
     queue = PatchQueue.for_process_group(len(patches), static=bool(args.start_from_prev))
+    holdout_snrs = []
     if args.datadim == "3d" and vol.ndim == 3:
         if (args.imgchannel or 1) != 1:
             raise _lib.DpiError("the device overlap-add path re-assembles single-channel 3-D volumes (imgchannel = 1)")
-        rec, mine = optimise_volume(args, patches, origins, vol.shape, pe, device, outpath, conc, queue)
+        rec, mine = optimise_volume(args, patches, origins, vol.shape, pe, device, outpath, conc, queue, holdout_snrs=holdout_snrs)
     else:
         # 2-D / 2.5-D slabs: result files only; rank 0 re-assembles them on the host like the reference does
         from .data import reconstruct_patches
@@ -457,11 +475,13 @@ def main(argv=None):
                 T.build_regularizer()
                 T.optimize(verbose=False)
             T.save_result()
+            _record_holdout(T, holdout_snrs)
             T.clean()
             mine.append(i)
         if world > 1:
             dist.barrier()
         rec = reconstruct_patches(args) if rank == 0 else None
+    _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
         print("rank 0: %d patches total, %d local; reconstructed volume %s saved" % (len(patches), len(mine), rec.shape))

@@ -89,6 +89,10 @@ _FLAGS = [
     (("--aa_smooth",), dict(type=float, required=False, default=2.0, help="Gaussian smoothing (std, samples) of the structure tensor")),
     (("--aa_dips",), dict(type=str, required=False, help="Optional .npy with a precomputed dip field (same shape as a section; "
                                                          "3-D: 2*C*T*X*Y values, the (t,x) dips then the (t,y) dips)")),
+    # self-validation (ours): held-out traces select the output and drive early stopping
+    (("--holdout",), dict(type=float, required=False, default=0.0,
+                          help="Fraction in [0, 0.5] of the known traces withheld from the loss (0 = off).  The output with the lowest misfit on "
+                               "them is kept and early stopping follows that misfit; each trace is drawn independently from the patch seed")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -119,6 +123,8 @@ def postprocess(args: Namespace) -> Namespace:
         args.earlystop_patience = args.epochs
     if args.netdir is None:
         args.netdir = []
+    if not 0.0 <= getattr(args, "holdout", 0.0) <= 0.5:
+        raise ValueError("--holdout must lie in [0, 0.5], got %r" % args.holdout)
     return args
 
 

@@ -7,7 +7,7 @@ import torch
 
 from .generic import ten_digit
 
-__all__ = ["snr", "pcorr", "History", "HistoryReg"]
+__all__ = ["snr", "pcorr", "History", "HistoryReg", "HistoryHoldout", "HistoryRegHoldout"]
 
 
 def _lib(output, target):
@@ -94,3 +94,41 @@ class HistoryReg:
         return "Loss : %s\nReg  : %s\nSNR  : %s\nPCORR: %s" % (self.loss, self.reg, self.snr, self.pcorr)
 
     __repr__ = __str__
+
+
+class _HoldoutColumns:
+    """val_loss / val_snr columns of a run with held-out traces (--holdout): the misfit and the SNR on the held-out samples."""
+    _vmsg = ", VAL = %.2e, VSNR = %+.2f dB"
+
+    def append_val(self, val_loss, val_snr):
+        self.val_loss.append(val_loss)
+        self.val_snr.append(val_snr)
+
+    def log_message(self, idx):
+        return super().log_message(idx) + self._vmsg % (self.val_loss[idx], self.val_snr[idx])
+
+    def __len__(self):
+        n = super().__len__()
+        assert len(self.val_loss) == len(self.val_snr) == n
+        return n
+
+    def __str__(self):
+        return super().__str__() + "\nVAL  : %s\nVSNR : %s" % (self.val_loss, self.val_snr)
+
+    __repr__ = __str__
+
+
+class HistoryHoldout(_HoldoutColumns, History):
+    """History of a run with --holdout."""
+
+    def __init__(self, epochs):
+        History.__init__(self, epochs)
+        self.val_loss, self.val_snr = [], []
+
+
+class HistoryRegHoldout(_HoldoutColumns, HistoryReg):
+    """HistoryReg of a run with --holdout and a regulariser (--aa_weight): val_loss stays the pure data misfit."""
+
+    def __init__(self, epochs):
+        HistoryReg.__init__(self, epochs)
+        self.val_loss, self.val_snr = [], []

@@ -43,7 +43,7 @@ extern "C" {
 #define DPI_CHAIN_STRIDE 5
 
 const char* dpi_last_error(void);
-/* ABI version (405 = dpi_hale_sections / dpi_structure_tensor_sections: the anti-aliasing add-on on 3-D patches; 404 = round 6: the ten
+/* ABI version (406 = dpi_masked_loss_holdout / dpi_loop_control_holdout: held-out traces, --holdout; 405 = dpi_hale_sections / dpi_structure_tensor_sections: the anti-aliasing add-on on 3-D patches; 404 = round 6: the ten
  * dpi_set_* tuning functions left the ABI for dpi_set_option): 300 = round 3 (dpi_conv_desc carries its own size as first field), 301 adds dpi_conv_fwd_ws / dpi_conv_bwd_data_ws /
  * dpi_conv_bwd_data_dual, 401 = dpi_pack_scratch_bytes / dpi_pack_release, 402 = dpi_pack_forget (round 5), 403 = dpi_join_bwd (round 5), 400 = round 4: dpi_conv_desc grows the `io` field (bf16 storage of activations) and the elementwise entry
  * points get `_io` twins that take the storage types of their tensors.  A binding checks `>=` the version it was written against and
@@ -304,6 +304,15 @@ int dpi_deconv4x4s2_bwd_weight(const float* x, const float* dy, int Cin, int Cou
 size_t dpi_loss_ws_doubles(size_t n);
 int dpi_masked_loss(const float* out, const float* img, const float* mask, size_t n, int kind,
                     float grad_scale, float* dout, double* ws, double* result, void* stream);
+/* ABI 406.  The same pass with held-out traces (--holdout).  The tensors are [C][T][S] (n = C*T*S: the device layout (1, C, T, S...)
+ * of a patch, one trace per (c, s)); sel (device, float[C][S]) is 1 on the held-out traces and 0 elsewhere.  With m_tr = mask * (1 - sel)
+ * and m_ho = mask * sel per sample, dout and result[0..7] are bit for bit those of dpi_masked_loss(out, img, m_tr, n, ...) — same grid, walk
+ * and accumulation order; neither mask is materialised — and the pass adds, with e = t - o:
+ *   result[8] = val_loss = sum |e m_ho| (kind 0) or sum (e m_ho)^2 (kind 1), divided by N_ho;
+ *   result[9] = val_snr  = 10 log10(sum (t m_ho)^2 / sum (e m_ho)^2);   result[10] = N_ho = number of samples with m_ho != 0.
+ * result: double[11].  ws: double[2 * dpi_loss_ws_doubles(n)]. */
+int dpi_masked_loss_holdout(const float* out, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
+                            int kind, float grad_scale, float* dout, double* ws, double* result, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ---------------------
  * Replaces torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step() (main.py:200,213) for a list of
@@ -327,6 +336,15 @@ int dpi_loop_control(const double* metrics, double* state, double* hist, int max
                      int* active, int* improved, int use_plateau, double factor, double threshold,
                      int patience, double min_lr, double lr_eps, int es_patience, double es_min_delta,
                      void* stream);
+/* ABI 406.  dpi_loop_control for a run with held-out traces: metrics = the 11 doubles of dpi_masked_loss_holdout, hist rows of six
+ * {loss, snr, pcorr, lr, val_loss, val_snr}.  *improved (best output) when val_loss <= val_min (the later iterate wins a tie) and
+ * EarlyStopping(percentage) / NaN stop follow val_loss; ReduceLROnPlateau follows the training loss metrics[0].
+ * state: double[10] {iter, loss_min (training), plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved, val_min, best_iter},
+ * zero-initialised except state[2] = +inf. */
+int dpi_loop_control_holdout(const double* metrics, double* state, double* hist, int max_iters, float* step_lr,
+                             int* active, int* improved, int use_plateau, double factor, double threshold,
+                             int patience, double min_lr, double lr_eps, int es_patience, double es_min_delta,
+                             void* stream);
 int dpi_copy_if(const int* flag, const float* src, float* dst, size_t n, void* stream);
 
 /* ---------------------------------------------------------------- input perturbation ------------
