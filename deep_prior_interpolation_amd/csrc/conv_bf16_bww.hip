@@ -18,7 +18,7 @@
 //     fragments of the rows it pairs with (kh = x row - dY row) for the three kw copies: 54 MFMAs per 12 + 6 fragment reads.
 //   * Per-chunk partial sums go to the workspace [chunk][Cout][Cin][27] (waves reduced through LDS first) and are summed in
 //     fixed order by dpi_reduce_chunks — deterministic, no atomics, as the fp32 kernels.
-#include "common.h"
+#include "conv_kernels.h"
 
 namespace {
 
@@ -309,8 +309,6 @@ __global__ __launch_bounds__(256, NS == 1 ? 2 : 1) void conv_bf16_bwd_weight_ker
 struct BwBPlan { int nth, ntw, ndc, dlen, nchunks; };
 
 }  // namespace
-
-bool dpi_bf16_force_all();
 
 static BwBPlan bf16_bww_plan(const dpi_conv_desc* d) {
   BwBPlan p{};

@@ -15,7 +15,7 @@
 // the workspace [chunk][Cout][Cin][27] and are summed in fixed order by dpi_reduce_chunks — deterministic, no atomics, as everywhere.
 // Applies when x and dy are bf16, precision = 1, no producer chain on x, W a multiple of 16 (an octet of ow never straddles a row, every
 // 16-byte load is aligned, W = 2 Wo); everything else keeps the fp32-MFMA kernel (conv_bwd_weight.hip).
-#include "common.h"
+#include "conv_kernels.h"
 
 namespace {
 

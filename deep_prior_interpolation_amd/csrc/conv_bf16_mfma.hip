@@ -20,7 +20,7 @@
 // the fp64 oracle at the fp32 path's own tolerance) at 16 / 6 = 2.7 x the fp32 matrix rate.
 // Workgroup = 4 waves = output tile 4x4x32 (or the small 1x8x16/32 variants for coarse levels), as in conv_mfma.hip; D layout,
 // epilogue (bias, BatchNorm {sum, sum^2} partials, gradient fan-in) are those of the fp32 kernel.
-#include "common.h"
+#include "conv_kernels.h"
 
 #include <climits>
 #include <iterator>
@@ -28,8 +28,6 @@
 #include <mutex>
 #include <tuple>
 #include <vector>
-
-void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo);
 
 namespace {
 
@@ -1088,7 +1086,6 @@ bool dpi_conv_bf16_usable(const dpi_conv_desc* d, bool flip) {
   return d->precision >= 1 && d->k == 3 && d->stride == 1 && bf16_pays(d, flip);
 }
 
-// whether dpi_conv_bf16_run adds a 1x1x1 second input in the same pass: bf16 arithmetic mode, 3-D, backward-data
 bool dpi_conv_bf16_second_ok(const dpi_conv_desc* d, bool flip) { return flip && d->precision == 1 && d->kd == 3 && dpi_conv_bf16_usable(d, flip); }
 
 int dpi_conv_bf16_stat_blocks(const dpi_conv_desc* d) {

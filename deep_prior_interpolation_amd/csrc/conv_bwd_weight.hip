@@ -8,42 +8,8 @@
 // lane, shared by the 4 waves through L1).  Each block walks a contiguous chunk of tiles, then reduces
 // its accumulators across the 64 lanes and writes one partial per (chunk, co, ci, tap); a second kernel
 // sums the chunk partials in fixed order (deterministic, no atomics).
-#include "common.h"
+#include "conv_kernels.h"
 #include <algorithm>
-
-void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo);
-size_t dpi_conv_bwd_weight_mfma_ws_floats(const dpi_conv_desc* d);
-bool dpi_conv_bwd_weight_mfma_swapped(const dpi_conv_desc* d, const float* chain);
-int dpi_conv_bwd_weight_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* dy, float* dw, float* ws,
-                                 hipStream_t st);
-size_t dpi_conv_pw_bwd_weight_mfma_ws_floats(const dpi_conv_desc* d);
-int dpi_conv_pw_bwd_weight_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* dy, float* dw, float* ws,
-                                    hipStream_t st);
-size_t dpi_conv_bwd_weight_smallco_ws_floats(const dpi_conv_desc* d);
-int dpi_conv_bwd_weight_smallco_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* dy, float* dw, float* ws,
-                                    hipStream_t st);
-bool dpi_conv_bf16_bww_usable(const dpi_conv_desc* d);
-size_t dpi_conv_bf16_bww_ws_floats(const dpi_conv_desc* d);
-int dpi_conv_bf16_bww_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* dy, float* dw, float* ws, hipStream_t st);
-// conv_bf16_bww_s2.hip: 3x3x3 stride 2, x and dy bf16, bf16 arithmetic, no chain
-bool dpi_conv_bf16_bww_s2_usable(const dpi_conv_desc* d);
-size_t dpi_conv_bf16_bww_s2_ws_floats(const dpi_conv_desc* d);
-int dpi_conv_bf16_bww_s2_run(const dpi_conv_desc* d, const float* x, const float* dy, float* dw, float* ws, hipStream_t st);
-static bool bw_use_smallco(const dpi_conv_desc* d) {
-  return d->k == 3 && d->kd == 3 && d->stride == 1 && d->Cout <= 5 && (size_t)d->D * d->H * d->W >= 32768 &&
-         (size_t)d->D * d->H * d->W < ((size_t)1 << 26);   // one 32-bit buffer offset spans the (<= 5) dY channels
-}
-// few output channels, input not chained: the MFMA kernel in its swapped orientation (X rows x (co, tap) columns)
-static bool bw_use_mfma_swapped(const dpi_conv_desc* d, const float* x_chain) {
-  return d->k == 3 && d->stride == 1 && d->Cin >= 8 && (size_t)d->D * d->H * d->W < ((size_t)1 << 25) &&
-         dpi_conv_bwd_weight_mfma_swapped(d, x_chain);
-}
-static int g_bw_mfma_min_cout = 8;
-extern "C" void dpi_set_bwd_weight_mfma_min_cout(int n) { g_bw_mfma_min_cout = n; }
-// the MFMA kernel addresses 16 dY channels through one 32-bit buffer offset: 16 * Vo * 4 bytes must stay below 2^31
-static bool bw_use_mfma(const dpi_conv_desc* d) {
-  return d->k == 3 && d->Cout >= g_bw_mfma_min_cout && (size_t)d->D * d->H * d->W < ((size_t)1 << 25);
-}
 
 namespace {
 
@@ -259,10 +225,11 @@ __global__ void reduce_chunks_kernel(const float* __restrict__ ws, float* __rest
   if (i < n && part == 0) out[i] = s;
 }
 
-struct BwPlan { int nchunks, tiles_per_chunk, ntiles, ntd, nth, ntw; size_t vox_per_chunk; };
+// chunking of the two VALU kernels of this file
+struct BwChunks { int nchunks, tiles_per_chunk, ntiles, ntd, nth, ntw; size_t vox_per_chunk; };
 
-BwPlan plan(const dpi_conv_desc* d) {
-  BwPlan p{};
+BwChunks bw_chunks(const dpi_conv_desc* d) {
+  BwChunks p{};
   int Do, Ho, Wo;
   dpi_conv_out_dims(d, &Do, &Ho, &Wo);
   const size_t per = (size_t)d->Cout * d->Cin * d->kd * d->k * d->k;
@@ -295,25 +262,40 @@ BwPlan plan(const dpi_conv_desc* d) {
 
 }  // namespace
 
+static int g_bw_mfma_min_cout = 8;
+extern "C" void dpi_set_bwd_weight_mfma_min_cout(int n) { g_bw_mfma_min_cout = n; }
+
+// ---- the plan of one launch ------------------------------------------------------------------------------------------------------------
+// Which kernel a backward-weight launch gets and the workspace floats that kernel needs.  THE ORDER OF THESE TESTS LIVES HERE ONLY.  Besides
+// the descriptor it depends on what only the launch knows: a chain on x or none, the addresses (alignment) of x and dy.  Knobs are read at every call.
+enum class BwKernel { Bf16S2, Bf16, Mfma, SmallCo, PwMfma, Direct };
+struct BwPlan { BwKernel kernel; size_t ws_floats; };
+static BwPlan bw_plan(const dpi_conv_desc* d, bool chained, uintptr_t x, uintptr_t dy) {
+  const size_t V = (size_t)d->D * d->H * d->W;
+  // 16-byte octets of both bf16 tensors straight into the MFMA, no chain
+  if (dpi_conv_bf16_bww_s2_usable(d) && !chained && ((x | dy) & 15) == 0) return {BwKernel::Bf16S2, dpi_conv_bf16_bww_s2_ws_floats(d)};
+  // staging loads of 4 values: 16 bytes from an fp32 tensor, 8 from a bf16 one; the fp32 kernels below stay the fallback for unaligned views
+  const uintptr_t misal = (x & ((d->io & DPI_IO_X_BF16) ? 7 : 15)) | (dy & ((d->io & DPI_IO_DY_BF16) ? 7 : 15));
+  if (dpi_conv_bf16_bww_usable(d) && misal == 0) return {BwKernel::Bf16, dpi_conv_bf16_bww_ws_floats(d)};
+  // the MFMA kernel addresses 16 dY channels through one 32-bit buffer offset: 16 * Vo * 4 bytes must stay below 2^31.
+  // Few output channels, input not chained: the same kernel in its swapped orientation (X rows x (co, tap) columns)
+  if (d->k == 3 && V < ((size_t)1 << 25) &&
+      (d->Cout >= g_bw_mfma_min_cout || (d->stride == 1 && d->Cin >= 8 && dpi_conv_bwd_weight_mfma_swapped(d, chained))))
+    return {BwKernel::Mfma, dpi_conv_bwd_weight_mfma_ws_floats(d)};
+  if (d->k == 3 && d->kd == 3 && d->stride == 1 && d->Cout <= 5 && V >= 32768 && V < ((size_t)1 << 26))   // one 32-bit buffer offset spans the (<= 5) dY channels
+    return {BwKernel::SmallCo, dpi_conv_bwd_weight_smallco_ws_floats(d)};
+  if (d->k == 1 && d->Cout >= g_bw_mfma_min_cout) return {BwKernel::PwMfma, dpi_conv_pw_bwd_weight_mfma_ws_floats(d)};
+  return {BwKernel::Direct, (size_t)bw_chunks(d).nchunks * d->Cout * d->Cin * d->kd * d->k * d->k};
+}
+
+// The caller sizes the workspace before it knows the chain and the addresses of a launch: the largest need over both answers to each
+// (so a bf16 path is sized for its fp32 fallback too).
 extern "C" size_t dpi_conv_bwd_weight_ws_floats(const dpi_conv_desc* d) {
   if (dpi_check_conv_desc(d) != DPI_OK) return 0;
-  if (dpi_conv_bf16_bww_s2_usable(d)) {       // whether it runs depends on the chain and the alignment given at launch: size for both
-    dpi_conv_desc f = *d;
-    f.precision = 0;
-    return std::max(dpi_conv_bf16_bww_s2_ws_floats(d), dpi_conv_bwd_weight_ws_floats(&f));
-  }
-  if (dpi_conv_bf16_bww_usable(d)) {          // the fp32 kernels stay the fallback for unaligned views: size for both
-    dpi_conv_desc f = *d;
-    f.precision = 0;
-    return std::max(dpi_conv_bf16_bww_ws_floats(d), dpi_conv_bwd_weight_ws_floats(&f));
-  }
-  if (bw_use_mfma(d)) return dpi_conv_bwd_weight_mfma_ws_floats(d);
-  // whether the swapped MFMA path runs depends on the chain given at launch: size for either
-  const size_t sw = bw_use_mfma_swapped(d, nullptr) ? dpi_conv_bwd_weight_mfma_ws_floats(d) : 0;
-  if (bw_use_smallco(d)) return std::max(sw, dpi_conv_bwd_weight_smallco_ws_floats(d));
-  if (d->k == 1 && d->Cout >= g_bw_mfma_min_cout) return dpi_conv_pw_bwd_weight_mfma_ws_floats(d);
-  const BwPlan p = plan(d);
-  return std::max(sw, (size_t)p.nchunks * d->Cout * d->Cin * d->kd * d->k * d->k);
+  size_t need = 0;
+  for (const bool chained : {false, true})
+    for (const uintptr_t addr : {(uintptr_t)0, (uintptr_t)1}) need = std::max(need, bw_plan(d, chained, addr, addr).ws_floats);
+  return need;
 }
 
 extern "C" int dpi_conv_bwd_weight(const dpi_conv_desc* d, const float* x, const float* x_chain, const float* dy,
@@ -323,49 +305,22 @@ extern "C" int dpi_conv_bwd_weight(const dpi_conv_desc* d, const float* x, const
   DPI_REQUIRE((d->k == 1 || d->k == 3) && (d->kd == d->k || d->kd == 1) && (d->stride == 1 || d->stride == 2),
               "conv_bwd_weight: unsupported k=%d kd=%d stride=%d", d->k, d->kd, d->stride);
   hipStream_t st = (hipStream_t)stream;
-  // staging loads of 4 values: 16 bytes from an fp32 tensor, 8 from a bf16 one
-  const uintptr_t misal = ((uintptr_t)x & ((d->io & DPI_IO_X_BF16) ? 7 : 15)) | ((uintptr_t)dy & ((d->io & DPI_IO_DY_BF16) ? 7 : 15));
-  if (dpi_conv_bf16_bww_s2_usable(d) && x_chain == nullptr && (((uintptr_t)x | (uintptr_t)dy) & 15) == 0) {
-    if (ws_floats < dpi_conv_bf16_bww_s2_ws_floats(d)) {
-      dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, dpi_conv_bf16_bww_s2_ws_floats(d));
-      return DPI_E_WORKSPACE;
-    }
-    return dpi_conv_bf16_bww_s2_run(d, x, dy, dw, ws, st);
-  }
-  if (dpi_conv_bf16_bww_usable(d) && misal == 0) {
-    if (ws_floats < dpi_conv_bf16_bww_ws_floats(d)) {
-      dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, dpi_conv_bf16_bww_ws_floats(d));
-      return DPI_E_WORKSPACE;
-    }
-    return dpi_conv_bf16_bww_run(d, x, x_chain, dy, dw, ws, st);
-  }
-  if (bw_use_mfma(d) || bw_use_mfma_swapped(d, x_chain)) {
-    if (ws_floats < dpi_conv_bwd_weight_mfma_ws_floats(d)) {
-      dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, dpi_conv_bwd_weight_mfma_ws_floats(d));
-      return DPI_E_WORKSPACE;
-    }
-    return dpi_conv_bwd_weight_mfma_run(d, x, x_chain, dy, dw, ws, st);
-  }
-  if (bw_use_smallco(d)) {
-    if (ws_floats < dpi_conv_bwd_weight_smallco_ws_floats(d)) {
-      dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, dpi_conv_bwd_weight_smallco_ws_floats(d));
-      return DPI_E_WORKSPACE;
-    }
-    return dpi_conv_bwd_weight_smallco_run(d, x, x_chain, dy, dw, ws, st);
-  }
-  if (d->k == 1 && d->Cout >= g_bw_mfma_min_cout) {
-    if (ws_floats < dpi_conv_pw_bwd_weight_mfma_ws_floats(d)) {
-      dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, dpi_conv_pw_bwd_weight_mfma_ws_floats(d));
-      return DPI_E_WORKSPACE;
-    }
-    return dpi_conv_pw_bwd_weight_mfma_run(d, x, x_chain, dy, dw, ws, st);
-  }
-  const BwPlan p = plan(d);
-  const size_t per = (size_t)d->Cout * d->Cin * d->kd * d->k * d->k;
-  if (ws_floats < per * p.nchunks) {
-    dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, per * p.nchunks);
+  const BwPlan plan = bw_plan(d, x_chain != nullptr, (uintptr_t)x, (uintptr_t)dy);
+  if (ws_floats < plan.ws_floats) {
+    dpi_set_error("conv_bwd_weight: workspace %zu < %zu floats", ws_floats, plan.ws_floats);
     return DPI_E_WORKSPACE;
   }
+  switch (plan.kernel) {
+    case BwKernel::Bf16S2: return dpi_conv_bf16_bww_s2_run(d, x, dy, dw, ws, st);
+    case BwKernel::Bf16: return dpi_conv_bf16_bww_run(d, x, x_chain, dy, dw, ws, st);
+    case BwKernel::Mfma: return dpi_conv_bwd_weight_mfma_run(d, x, x_chain, dy, dw, ws, st);
+    case BwKernel::SmallCo: return dpi_conv_bwd_weight_smallco_run(d, x, x_chain, dy, dw, ws, st);
+    case BwKernel::PwMfma: return dpi_conv_pw_bwd_weight_mfma_run(d, x, x_chain, dy, dw, ws, st);
+    case BwKernel::Direct: break;
+  }
+  // the VALU kernels of this file
+  const BwChunks p = bw_chunks(d);
+  const size_t per = (size_t)d->Cout * d->Cin * d->kd * d->k * d->k;
   int Do, Ho, Wo;
   dpi_conv_out_dims(d, &Do, &Ho, &Wo);
   if (d->k == 1) {

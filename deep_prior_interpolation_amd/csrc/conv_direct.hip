@@ -11,7 +11,7 @@
 //
 // The same kernel serves backward-data of stride-1 convolutions (FLIP: taps reversed, channel roles
 // swapped through the weight strides).
-#include "common.h"
+#include "conv_kernels.h"
 
 namespace {
 
@@ -428,7 +428,17 @@ void launch_pw_co(const PwArgs& a, int co_b, dim3 grid, hipStream_t st) {
   }
 }
 
-int check_desc(const dpi_conv_desc* d) { return dpi_check_conv_desc(d); }
+// the two VALU kernels of this file: one BatchNorm partial row per spatial tile / per 1024 voxels (256 threads x 4 voxels)
+constexpr size_t kPwVoxPerBlock = 1024;
+int direct_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
+  int Do, Ho, Wo;
+  dpi_conv_out_dims(d, &Do, &Ho, &Wo);
+  const Geo g = conv_geo(d->kd, d->stride);
+  *ntd = cdiv(Do, g.tz); *nth = cdiv(Ho, g.ty); *ntw = cdiv(Wo, g.txow);
+  return *ntd * *nth * *ntw;
+}
+int direct_stat_blocks(const dpi_conv_desc* d) { int a, b, c; return direct_tiles(d, &a, &b, &c); }
+int pw_stat_blocks(const dpi_conv_desc* d) { return (int)cdivz((size_t)d->D * d->H * d->W, kPwVoxPerBlock); }
 
 }  // namespace
 
@@ -451,43 +461,6 @@ int dpi_check_conv_desc(const dpi_conv_desc* d) {
   return DPI_OK;
 }
 
-// MFMA stencil path (conv_mfma.hip): k = 3, stride 1, enough output channels to fill a 16-row MFMA tile
-int dpi_conv_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
-                      double* partials, bool flip, int accumulate, float* ws, size_t ws_floats, hipStream_t st, const MfmaSecond* sec = nullptr);
-size_t dpi_conv_mfma_ws_floats(const dpi_conv_desc* d, bool flip);
-bool dpi_conv_mfma_second_ok(const dpi_conv_desc* d, bool flip, int C2, bool have_ws);
-void dpi_conv_pw_mfma_plan(size_t V, int cout, int* vox_per_block, int* mt);
-bool dpi_conv_fewco_usable(const dpi_conv_desc* d);
-bool dpi_conv_q4_usable(const dpi_conv_desc* d, bool flip);
-int dpi_conv_q4_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw);
-int dpi_conv_q4_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
-                    double* partials, bool flip, int accumulate, hipStream_t st);
-int dpi_conv_fewco_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw);
-int dpi_conv_fewco_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
-                            double* partials, hipStream_t st);
-static int g_fewco_mfma = 1;
-extern "C" void dpi_set_fewco_mfma(int on) { g_fewco_mfma = on; }
-int dpi_conv_pw_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
-                         double* partials, bool flip, int accumulate, hipStream_t st);
-int dpi_conv_bwd_data_s2_mfma_run(const dpi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, hipStream_t st);
-void dpi_mfma_variant(const dpi_conv_desc* d, int cout, int* nr, int* nh);
-int dpi_mfma_tiles(const dpi_conv_desc* d, int nr, int nh, int* ntd, int* nth, int* ntw);
-bool dpi_mfma_half_tile(const dpi_conv_desc* d, bool flip);
-bool dpi_conv_bf16_usable(const dpi_conv_desc* d, bool flip);
-// conv_bf16_mfma.hip: 3x3x3 stride-2 forward, bf16 x and y, bf16 arithmetic
-bool dpi_conv_bf16_s2_usable(const dpi_conv_desc* d);
-int dpi_conv_bf16_s2_stat_blocks(const dpi_conv_desc* d);
-bool dpi_conv_bf16_s2_bwd_usable(const dpi_conv_desc* d);
-int dpi_conv_bf16_s2_bwd_run(const dpi_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate, hipStream_t st);
-int dpi_conv_bf16_s2_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y, double* partials,
-                         hipStream_t st);
-int dpi_conv_bf16_stat_blocks(const dpi_conv_desc* d);
-int dpi_conv_bf16_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
-                      double* partials, bool flip, int accumulate, hipStream_t st, const MfmaSecond* sec = nullptr);
-bool dpi_conv_bf16_second_ok(const dpi_conv_desc* d, bool flip);
-static int g_mfma_min_cout = 8;
-extern "C" void dpi_set_mfma_min_cout(int n) { g_mfma_min_cout = n; }
-
 void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo) {
   const int p = (d->k - 1) / 2, pd = (d->kd - 1) / 2, sd = d->kd > 1 ? d->stride : 1;
   *Do = (d->D + 2 * pd - d->kd) / sd + 1;
@@ -495,65 +468,71 @@ void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo) {
   *Wo = (d->W + 2 * p - d->k) / d->stride + 1;
 }
 
-extern "C" int dpi_conv_fwd_stat_blocks(const dpi_conv_desc* d) {
-  if (check_desc(d) != DPI_OK) return 0;
-  int Do, Ho, Wo;
-  dpi_conv_out_dims(d, &Do, &Ho, &Wo);
-  if (dpi_conv_bf16_s2_usable(d)) return dpi_conv_bf16_s2_stat_blocks(d);
-  if (dpi_conv_bf16_usable(d, false)) return dpi_conv_bf16_stat_blocks(d);
-  if (dpi_conv_q4_usable(d, false)) { int a, b, c; return dpi_conv_q4_tiles(d, &a, &b, &c); }
-  if (d->k == 1 && d->Cout >= g_mfma_min_cout) {
-    int vpb, mt;
-    dpi_conv_pw_mfma_plan((size_t)Do * Ho * Wo, d->Cout, &vpb, &mt);
-    return (int)cdivz((size_t)Do * Ho * Wo, vpb);
-  }
-  if (d->k == 1) return (int)cdivz((size_t)Do * Ho * Wo, 1024);
-  if (d->k == 3 && d->Cout >= g_mfma_min_cout) {
-    int nr, nh, a, b, c;
-    dpi_mfma_variant(d, d->Cout, &nr, &nh);
-    if (dpi_mfma_half_tile(d, false)) nr = 4;
-    return dpi_mfma_tiles(d, nr, nh, &a, &b, &c);
-  }
-  if (g_fewco_mfma && !(d->io & (DPI_IO_X_BF16 | DPI_IO_Y_BF16)) && dpi_conv_fewco_usable(d)) { int a, b, c; return dpi_conv_fewco_tiles(d, &a, &b, &c); }
-  const Geo g = conv_geo(d->kd, d->stride);
-  return cdiv(Do, g.tz) * cdiv(Ho, g.ty) * cdiv(Wo, g.txow);
+static int g_fewco_mfma = 1;
+extern "C" void dpi_set_fewco_mfma(int on) { g_fewco_mfma = on; }
+static int g_mfma_min_cout = 8;
+extern "C" void dpi_set_mfma_min_cout(int n) { g_mfma_min_cout = n; }
+
+// ---- the plan of one launch ------------------------------------------------------------------------------------------------------------
+// Which kernel family a forward (flip = false) or stride-1 backward-data (flip = true: dy passed as x, channel roles swapped) launch gets,
+// how many BatchNorm partial rows its epilogue writes and what workspace it can use.  THE ORDER OF THESE TESTS LIVES HERE ONLY: conv_run, the
+// sizing queries and the fused-pair decision of dpi_conv_bwd_data_dual ask conv_plan.  The knobs (dpi_set_option) are read at every call.
+enum class ConvKernel { Bf16S2, Bf16, Q4, Mfma, PwMfma, Fewco, Pw, Direct };
+struct ConvPlan { ConvKernel kernel; int stat_blocks; size_t ws_floats; };     // (ws: the input-channel split of the fp32 MFMA stencil family)
+static ConvPlan conv_plan(const dpi_conv_desc* d, bool flip, int accumulate) {
+  const int cout = flip ? d->Cin : d->Cout;
+  const bool fresh_fwd = !flip && !accumulate;
+  if (fresh_fwd && dpi_conv_bf16_s2_usable(d)) return {ConvKernel::Bf16S2, dpi_conv_bf16_s2_stat_blocks(d), 0};
+  if (dpi_conv_bf16_usable(d, flip)) return {ConvKernel::Bf16, dpi_conv_bf16_stat_blocks(d), 0};
+  if (dpi_conv_q4_usable(d, flip)) return {ConvKernel::Q4, dpi_conv_q4_stat_blocks(d), 0};
+  // enough output channels to fill a 16-row MFMA tile (stride 2 has a kernel of its own for backward-data: dpi_conv_bwd_data_ws)
+  if (d->k == 3 && cout >= g_mfma_min_cout && (d->stride == 1 || !flip))
+    return {ConvKernel::Mfma, dpi_conv_mfma_stat_blocks(d, flip), dpi_conv_mfma_ws_floats(d, flip)};
+  if (d->k == 1 && cout >= g_mfma_min_cout) return {ConvKernel::PwMfma, dpi_conv_pw_mfma_stat_blocks(d), 0};
+  if (fresh_fwd && g_fewco_mfma && !dpi_io_in(d, flip) && !dpi_io_out(d, flip) && dpi_conv_fewco_usable(d))
+    return {ConvKernel::Fewco, dpi_conv_fewco_stat_blocks(d), 0};
+  if (d->k == 1) return {ConvKernel::Pw, pw_stat_blocks(d), 0};
+  return {ConvKernel::Direct, direct_stat_blocks(d), 0};
 }
 
-// which launches take the fp32-MFMA stencil path of conv_mfma.hip (the order of the tests in conv_run)
-static bool takes_mfma_path(const dpi_conv_desc* d, bool flip) {
-  const int cout = flip ? d->Cin : d->Cout;
-  if (dpi_conv_bf16_usable(d, flip) || dpi_conv_q4_usable(d, flip) || (!flip && dpi_conv_bf16_s2_usable(d))) return false;
-  return d->k == 3 && cout >= g_mfma_min_cout && (d->stride == 1 || !flip);
+extern "C" int dpi_conv_fwd_stat_blocks(const dpi_conv_desc* d) {
+  return dpi_check_conv_desc(d) == DPI_OK ? conv_plan(d, false, 0).stat_blocks : 0;
+}
+
+extern "C" size_t dpi_conv_fwd_ws_floats(const dpi_conv_desc* d) {
+  return dpi_check_conv_desc(d) == DPI_OK ? conv_plan(d, false, 0).ws_floats : 0;
+}
+
+extern "C" size_t dpi_conv_bwd_data_ws_floats(const dpi_conv_desc* d) {      // (stride 2 is not conv_plan's: dpi_conv_bwd_data_ws)
+  return dpi_check_conv_desc(d) == DPI_OK && d->stride == 1 ? conv_plan(d, true, 0).ws_floats : 0;
 }
 
 static int conv_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias,
                     float* y, double* partials, bool flip, int accumulate, float* ws, size_t ws_floats, hipStream_t st) {
-  // For flip (backward-data of a stride-1 conv) the caller passes dy as x and swaps channel roles:
-  // "Cin" of this launch = d->Cout, "Cout" = d->Cin, spatial dims unchanged.
-  int Do, Ho, Wo;
-  dpi_conv_out_dims(d, &Do, &Ho, &Wo);
+  switch (conv_plan(d, flip, accumulate).kernel) {
+    case ConvKernel::Bf16S2: return dpi_conv_bf16_s2_run(d, x, chain, w, bias, y, partials, st);
+    case ConvKernel::Bf16: return dpi_conv_bf16_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
+    case ConvKernel::Q4: return dpi_conv_q4_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
+    case ConvKernel::Mfma: return dpi_conv_mfma_run(d, x, chain, w, bias, y, partials, flip, accumulate, ws, ws_floats, st);
+    case ConvKernel::PwMfma: return dpi_conv_pw_mfma_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
+    case ConvKernel::Fewco: return dpi_conv_fewco_mfma_run(d, x, chain, w, bias, y, partials, st);
+    case ConvKernel::Pw: case ConvKernel::Direct: break;      // the VALU kernels of this file, below
+  }
+  // for flip "Cin" of the launch = d->Cout, "Cout" = d->Cin, spatial dims unchanged
   const int taps = d->kd * d->k * d->k;
   const int cin = flip ? d->Cout : d->Cin, cout = flip ? d->Cin : d->Cout;
   const long w_out = flip ? taps : (long)d->Cin * taps, w_in = flip ? (long)d->Cin * taps : taps;
-  if (!flip && !accumulate && dpi_conv_bf16_s2_usable(d)) return dpi_conv_bf16_s2_run(d, x, chain, w, bias, y, partials, st);
-  if (dpi_conv_bf16_usable(d, flip)) return dpi_conv_bf16_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
-  if (dpi_conv_q4_usable(d, flip)) return dpi_conv_q4_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
   const int xb = dpi_io_in(d, flip), yb = dpi_io_out(d, flip);
-  if (d->k == 3 && cout >= g_mfma_min_cout && (d->stride == 1 || !flip))
-    return dpi_conv_mfma_run(d, x, chain, w, bias, y, partials, flip, accumulate, ws, ws_floats, st);
-  if (d->k == 1 && cout >= g_mfma_min_cout) return dpi_conv_pw_mfma_run(d, x, chain, w, bias, y, partials, flip, accumulate, st);
-  if (!flip && !accumulate && g_fewco_mfma && !xb && !yb && dpi_conv_fewco_usable(d)) return dpi_conv_fewco_mfma_run(d, x, chain, w, bias, y, partials, st);
   const int co_b = pick_co_b(cout);
   if (d->k == 1) {
-    PwArgs a{x, chain, w, bias, y, partials, cin, cout, (size_t)Do * Ho * Wo, w_out, w_in, accumulate, xb, yb};
-    dim3 grid((unsigned)cdivz(a.V, 1024), cdiv(cout, co_b));
+    PwArgs a{x, chain, w, bias, y, partials, cin, cout, (size_t)d->D * d->H * d->W, w_out, w_in, accumulate, xb, yb};
+    dim3 grid((unsigned)cdivz(a.V, kPwVoxPerBlock), cdiv(cout, co_b));
     launch_pw_co(a, co_b, grid, st);
     return dpi_check_launch("conv_pw");
   }
-  const Geo g = conv_geo(d->kd, d->stride);
-  ConvArgs a{x, chain, w, bias, y, partials, cin, cout, d->D, d->H, d->W, Do, Ho, Wo,
-             cdiv(Do, g.tz), cdiv(Ho, g.ty), cdiv(Wo, g.txow), w_out, w_in, accumulate, xb, yb};
-  dim3 grid(a.ntd * a.nth * a.ntw, cdiv(cout, co_b));
+  ConvArgs a{x, chain, w, bias, y, partials, cin, cout, d->D, d->H, d->W, 0, 0, 0, 0, 0, 0, w_out, w_in, accumulate, xb, yb};
+  dpi_conv_out_dims(d, &a.Do, &a.Ho, &a.Wo);
+  dim3 grid(direct_tiles(d, &a.ntd, &a.nth, &a.ntw), cdiv(cout, co_b));
   if (d->kd == 3) {
     if (d->stride == 1) { if (flip) launch_co<3, 1, true>(a, co_b, grid, st); else launch_co<3, 1, false>(a, co_b, grid, st); }
     else launch_co<3, 2, false>(a, co_b, grid, st);
@@ -564,19 +543,9 @@ static int conv_run(const dpi_conv_desc* d, const float* x, const float* chain, 
   return dpi_check_launch("conv_direct");
 }
 
-extern "C" size_t dpi_conv_fwd_ws_floats(const dpi_conv_desc* d) {
-  if (check_desc(d) != DPI_OK) return 0;
-  return takes_mfma_path(d, false) ? dpi_conv_mfma_ws_floats(d, false) : 0;
-}
-
-extern "C" size_t dpi_conv_bwd_data_ws_floats(const dpi_conv_desc* d) {
-  if (check_desc(d) != DPI_OK || d->stride != 1) return 0;
-  return takes_mfma_path(d, true) ? dpi_conv_mfma_ws_floats(d, true) : 0;
-}
-
 extern "C" int dpi_conv_fwd_ws(const dpi_conv_desc* d, const float* x, const float* x_chain, const float* w, const float* bias, float* y,
                                double* stat_partials, float* ws, size_t ws_floats, void* stream) {
-  if (int e = check_desc(d)) return e;
+  if (int e = dpi_check_conv_desc(d)) return e;
   DPI_REQUIRE(x && w && y, "conv_fwd: null tensor");
   DPI_REQUIRE(ws || ws_floats == 0, "conv_fwd: workspace size without a workspace");
   return conv_run(d, x, x_chain, w, bias, y, stat_partials, false, 0, ws, ws_floats, (hipStream_t)stream);
@@ -597,20 +566,22 @@ static int g_dual = getenv("DPI_NO_DUAL") ? 0 : 1;
 extern "C" void dpi_set_dual_bwd_data(int on) { g_dual = on; }
 extern "C" int dpi_conv_bwd_data_dual(const dpi_conv_desc* d3, const float* dy3, const float* w3, const dpi_conv_desc* d1, const float* dy1,
                                       const float* w1, float* dx, int accumulate, float* ws, size_t ws_floats, void* stream) {
-  if (int e = check_desc(d3)) return e;
-  if (int e = check_desc(d1)) return e;
+  if (int e = dpi_check_conv_desc(d3)) return e;
+  if (int e = dpi_check_conv_desc(d1)) return e;
   DPI_REQUIRE(dy3 && w3 && dy1 && w1 && dx, "conv_bwd_data_dual: null tensor");
   DPI_REQUIRE(ws || ws_floats == 0, "conv_bwd_data_dual: workspace size without a workspace");
   DPI_REQUIRE(d3->k == 3 && d1->k == 1 && d3->stride == 1 && d1->stride == 1, "conv_bwd_data_dual: needs a 3x3(x3) and a 1x1(x1) stride-1 layer");
   DPI_REQUIRE(d3->Cin == d1->Cin && d3->D == d1->D && d3->H == d1->H && d3->W == d1->W, "conv_bwd_data_dual: the two layers read different tensors");
   hipStream_t st = (hipStream_t)stream;
   DPI_REQUIRE((d3->io & (DPI_IO_DX_BF16 | DPI_IO_X_BF16)) == (d1->io & (DPI_IO_DX_BF16 | DPI_IO_X_BF16)), "conv_bwd_data_dual: the two layers disagree on the storage type of their input");
-  if (g_dual && dpi_conv_bf16_second_ok(d3, true) && (d3->io & DPI_IO_DY_BF16) == (d1->io & DPI_IO_DY_BF16)) {
+  // one fused launch where the family that conv_plan gives the 3x3(x3) layer can take the 1x1(x1) term along, else two launches
+  const ConvKernel k3 = conv_plan(d3, true, accumulate).kernel;
+  if (g_dual && k3 == ConvKernel::Bf16 && dpi_conv_bf16_second_ok(d3, true) && (d3->io & DPI_IO_DY_BF16) == (d1->io & DPI_IO_DY_BF16)) {
     // bf16 arithmetic mode: the 1x1x1 term as extra K blocks of the bf16-MFMA kernel (conv_bf16_mfma.hip)
     const MfmaSecond sec{dy1, w1, d1->Cout, 1, (long)d1->Cin};
     return dpi_conv_bf16_run(d3, dy3, nullptr, w3, nullptr, dx, nullptr, true, accumulate, st, &sec);
   }
-  if (g_dual && takes_mfma_path(d3, true) && dpi_conv_mfma_second_ok(d3, true, d1->Cout, ws != nullptr)) {
+  if (g_dual && k3 == ConvKernel::Mfma && dpi_conv_mfma_second_ok(d3, true, d1->Cout, ws != nullptr)) {
     // W2[ci][co1] = w1[co1][ci]: rows of this launch are the layers' INPUT channels
     const MfmaSecond sec{dy1, w1, d1->Cout, 1, (long)d1->Cin};
     return dpi_conv_mfma_run(d3, dy3, nullptr, w3, nullptr, dx, nullptr, true, accumulate, nullptr, 0, st, &sec);
@@ -621,11 +592,13 @@ extern "C" int dpi_conv_bwd_data_dual(const dpi_conv_desc* d3, const float* dy3,
 
 extern "C" int dpi_conv_bwd_data_ws(const dpi_conv_desc* d, const float* dy, const float* w, float* dx,
                                     int accumulate, float* ws, size_t ws_floats, void* stream) {
-  if (int e = check_desc(d)) return e;
+  if (int e = dpi_check_conv_desc(d)) return e;
   DPI_REQUIRE(dy && w && dx, "conv_bwd_data: null tensor");
   DPI_REQUIRE(ws || ws_floats == 0, "conv_bwd_data: workspace size without a workspace");
   hipStream_t st = (hipStream_t)stream;
   if (d->stride == 1) return conv_run(d, dy, nullptr, w, nullptr, dx, nullptr, true, accumulate, ws, ws_floats, st);
+  // NOT PART OF conv_plan: stride 2 has three backward-data kernels of its own, and the first choice depends on the alignment of the
+  // pointers of this launch.
   // bf16 tensors in the bf16 arithmetic mode: parity-class GEMMs on the bf16 MFMA (8-byte pieces of dy, dword stores of dx)
   if (dpi_conv_bf16_s2_bwd_usable(d) && ((uintptr_t)dy & 7) == 0 && ((uintptr_t)dx & 3) == 0) return dpi_conv_bf16_s2_bwd_run(d, dy, w, dx, accumulate, st);
   if (d->Cin >= g_mfma_min_cout) return dpi_conv_bwd_data_s2_mfma_run(d, dy, w, dx, accumulate, st);

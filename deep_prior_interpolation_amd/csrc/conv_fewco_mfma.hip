@@ -10,9 +10,7 @@
 //   B (input)  : lane (k = l>>4 -> ci, column j = l&15)                                           LDS halo tile
 //   D          : lane (column j, rows 4*(l>>4) + r) -> co = l>>4, kw = r: one lane holds the three kw partials of its co
 // Tile: 4 waves = 4 depth slices x 8 rows x 48 input columns (3 column blocks) -> 46 output columns.
-#include "common.h"
-
-void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo);
+#include "conv_kernels.h"
 
 namespace {
 
@@ -194,15 +192,16 @@ bool dpi_conv_fewco_usable(const dpi_conv_desc* d) {
          (size_t)d->D * d->H * d->W < ((size_t)1 << 29);
 }
 
-int dpi_conv_fewco_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
+static int fewco_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
   *ntd = cdiv(d->D, TZ); *nth = cdiv(d->H, NR); *ntw = cdiv(d->W, TWO);
   return *ntd * *nth * *ntw;
 }
+int dpi_conv_fewco_stat_blocks(const dpi_conv_desc* d) { int a, b, c; return fewco_tiles(d, &a, &b, &c); }
 
 int dpi_conv_fewco_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
                             double* partials, hipStream_t st) {
   FcArgs a{x, chain, w, bias, y, partials, d->Cin, d->Cout, d->D, d->H, d->W, 0, 0, 0};
-  const int ntiles = dpi_conv_fewco_tiles(d, &a.ntd, &a.nth, &a.ntw);
+  const int ntiles = fewco_tiles(d, &a.ntd, &a.nth, &a.ntw);
   conv_fewco_mfma_kernel<<<ntiles, 256, 0, st>>>(a);
   return dpi_check_launch("conv_fewco_mfma");
 }

@@ -15,9 +15,7 @@
 // Workgroup = 4 waves = output tile 4x8x32 (3-D; wave w owns depth slice w) or 1x32x32 (2-D; wave w owns 8 rows);
 // each wave keeps 16 voxel tiles x MT channel tiles of accumulators.  Every LDS value is read once per chunk and
 // feeds up to 3 (kh) x MT MFMAs.
-#include "common.h"
-
-void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo);
+#include "conv_kernels.h"
 
 namespace {
 
@@ -1296,10 +1294,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 }  // namespace
 
-// ---- host-side entry points used by the dispatchers in conv_direct.hip / conv_bwd_weight.hip ---------------------------
+// ---- host-side entry points used by the dispatchers in conv_direct.hip / conv_bwd_weight.hip (conv_kernels.h) ---------
 // variant selection: big tiles while they still give >= 512 workgroups, else the small-tile kernels; stride 2 always
 // uses the small tiles (its halo tile is 4x larger)
-void dpi_mfma_variant(const dpi_conv_desc* d, int cout, int* nr, int* nh) {
+static void dpi_mfma_variant(const dpi_conv_desc* d, int cout, int* nr, int* nh) {
   int Do, Ho, Wo;
   dpi_conv_out_dims(d, &Do, &Ho, &Wo);
   const int tz = d->kd == 3 ? 4 : 1, ty = d->kd == 3 ? 8 : 32;
@@ -1311,7 +1309,7 @@ void dpi_mfma_variant(const dpi_conv_desc* d, int cout, int* nr, int* nh) {
 // Half-height tiles (4 x 4 x 32, ~115-140 VGPRs, 3-4 waves / SIMD) instead of the persistent 4 x 8 x 32 variant: measured
 // 3-8 % faster for backward-data of long channel loops and, with the tap-packed tail, for forward layers with 4m + 1 input
 // channels (25 -> 16: 108.9 -> 111.9 TFLOP/s); the big tile stays ahead for the other forward layers (51 -> 32).
-bool dpi_mfma_half_tile(const dpi_conv_desc* d, bool flip) {
+static bool dpi_mfma_half_tile(const dpi_conv_desc* d, bool flip) {
   const int cin = flip ? d->Cout : d->Cin, cout = flip ? d->Cin : d->Cout;
   int nr, nh;
   dpi_mfma_variant(d, cout, &nr, &nh);
@@ -1323,7 +1321,7 @@ bool dpi_mfma_half_tile(const dpi_conv_desc* d, bool flip) {
   return flip || ((cin & 3) == 1);
 }
 
-int dpi_mfma_tiles(const dpi_conv_desc* d, int nr, int nh, int* ntd, int* nth, int* ntw) {
+static int dpi_mfma_tiles(const dpi_conv_desc* d, int nr, int nh, int* ntd, int* nth, int* ntw) {
   int Do, Ho, Wo;
   dpi_conv_out_dims(d, &Do, &Ho, &Wo);
   const bool slices = d->kd == 3 && nr >= 4;
@@ -1331,6 +1329,17 @@ int dpi_mfma_tiles(const dpi_conv_desc* d, int nr, int nh, int* ntd, int* nth, i
   *ntd = cdiv(Do, tz); *nth = cdiv(Ho, ty); *ntw = cdiv(Wo, 16 * nh);
   return *ntd * *nth * *ntw;
 }
+
+// the tiling of one forward / backward-data launch: one BatchNorm partial row per tile
+struct MfmaTiling { int nr, nh, ntd, nth, ntw, ntiles; };
+static MfmaTiling mfma_tiling(const dpi_conv_desc* d, bool flip) {
+  MfmaTiling t{};
+  dpi_mfma_variant(d, flip ? d->Cin : d->Cout, &t.nr, &t.nh);
+  if (dpi_mfma_half_tile(d, flip)) t.nr = 4;
+  t.ntiles = dpi_mfma_tiles(d, t.nr, t.nh, &t.ntd, &t.nth, &t.ntw);
+  return t;
+}
+int dpi_conv_mfma_stat_blocks(const dpi_conv_desc* d, bool flip) { return mfma_tiling(d, flip).ntiles; }
 
 template <int KD, bool FLIP, bool IOB = false>
 static void launch_variant(const MArgs& a_in, int nr, int nh, int stride, dim3 grid_in, hipStream_t st) {
@@ -1408,7 +1417,7 @@ extern "C" int dpi_debug_read_trace(long long* out) { return (int)hipMemcpyFromS
 // with 1 / nsplit of the serial chain.  Returns the number of splits (1: none).
 static int g_splitk = getenv("DPI_SPLITK") ? atoi(getenv("DPI_SPLITK")) : 1;
 extern "C" void dpi_set_splitk(int on) { g_splitk = on; }
-int dpi_mfma_splitk(const dpi_conv_desc* d, bool flip) {
+static int dpi_mfma_splitk(const dpi_conv_desc* d, bool flip) {
   if (!g_splitk || d->k != 3) return 1;
   const int cin = flip ? d->Cout : d->Cin, cout = flip ? d->Cin : d->Cout;
   int nr, nh, a, b, c;
@@ -1433,7 +1442,6 @@ size_t dpi_conv_mfma_ws_floats(const dpi_conv_desc* d, bool flip) {
   return (size_t)ns * (flip ? d->Cin : d->Cout) * Do * Ho * Wo;
 }
 
-// whether dpi_conv_mfma_run can add a 1x1x1 second input of C2 channels in the same pass (MfmaSecond)
 bool dpi_conv_mfma_second_ok(const dpi_conv_desc* d, bool flip, int C2, bool have_ws) {
   int Do, Ho, Wo;
   dpi_conv_out_dims(d, &Do, &Ho, &Wo);
@@ -1451,10 +1459,9 @@ int dpi_conv_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain
   const long w_out = flip ? taps : (long)d->Cin * taps, w_in = flip ? (long)d->Cin * taps : taps;
   MArgs a{x, chain, w, bias, y, partials, cin, cout, d->D, d->H, d->W, 0, 0, 0, w_out, w_in, accumulate, 0, nullptr, nullptr, 0, 0, 0,
           dpi_io_in(d, flip), dpi_io_out(d, flip)};
-  int nr, nh;
-  dpi_mfma_variant(d, cout, &nr, &nh);
-  if (dpi_mfma_half_tile(d, flip)) nr = 4;
-  const int ntiles = dpi_mfma_tiles(d, nr, nh, &a.ntd, &a.nth, &a.ntw);
+  const MfmaTiling t = mfma_tiling(d, flip);
+  const int nr = t.nr, nh = t.nh, ntiles = t.ntiles;
+  a.ntd = t.ntd; a.nth = t.nth; a.ntw = t.ntw;
   dim3 grid(ntiles, cdiv(cout, 16));
   if (sec) { a.x2 = sec->x2; a.w2 = sec->w2; a.C2 = sec->C2; a.w2_co_stride = sec->w2_co_stride; a.w2_c_stride = sec->w2_c_stride; }
   const int nsplit = (ws && !sec) ? dpi_mfma_splitk(d, flip) : 1;
@@ -1542,7 +1549,7 @@ size_t dpi_conv_bwd_weight_mfma_ws_floats(const dpi_conv_desc* d) {
   const int n0 = mfma_bw_plan(d, false).nchunks, n1 = mfma_bw_swap_better(d) ? mfma_bw_plan(d, true).nchunks : 0;
   return (size_t)(n0 > n1 ? n0 : n1) * d->Cout * d->Cin * d->kd * 9;     // either orientation (the chain decides at run time)
 }
-bool dpi_conv_bwd_weight_mfma_swapped(const dpi_conv_desc* d, const float* chain) { return chain == nullptr && mfma_bw_swap_better(d); }
+bool dpi_conv_bwd_weight_mfma_swapped(const dpi_conv_desc* d, bool chained) { return !chained && mfma_bw_swap_better(d); }
 
 // dyb class of a bf16 row operand: 1 when every 4-element piece starts 4-byte aligned (even row length and channel size, aligned base)
 static int bf16_row_class(const void* base, int row_len, size_t channel_elems) {
@@ -1551,7 +1558,7 @@ static int bf16_row_class(const void* base, int row_len, size_t channel_elems) {
 
 int dpi_conv_bwd_weight_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* dy, float* dw, float* ws,
                                  hipStream_t st) {
-  const bool swap = dpi_conv_bwd_weight_mfma_swapped(d, chain);     // the chain can only be applied to the staged tensor
+  const bool swap = dpi_conv_bwd_weight_mfma_swapped(d, chain != nullptr);     // the chain can only be applied to the staged tensor
   const MfmaBwPlan p = mfma_bw_plan(d, swap);
   BwMArgs a{x, chain, dy, ws, d->Cin, d->Cout, d->D, d->H, d->W, p.ntd, p.nth, p.ntw, p.ntiles, p.tiles_per_chunk, 0, 0, 0, p.nchunks,
             (d->io & DPI_IO_X_BF16) != 0, (d->io & DPI_IO_DY_BF16) != 0};

@@ -10,7 +10,7 @@
 //   bwd-weight: D[co 16][ci 16] += A[co][vox 4] * B[vox 4][ci]
 //              lane loads float4 dy[co = lj][v0 + 4*lk .. +3] and x[ci = lj][v0 + 4*lk .. +3]; element e pairs the voxels
 //              {v0 + 4*lk + e} of both operands.
-#include "common.h"
+#include "conv_kernels.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -491,7 +491,7 @@ PwBwPlan pw_bw_plan(const dpi_conv_desc* d) {
 // 1024 voxels x up to 64 output channels (the input tile is read once for all of them); the coarse levels of the U-Net
 // (a few thousand voxels, hundreds of channels) would leave most CUs idle that way, so they get 256-voxel workgroups
 // and, if that is still not ~4 waves per CU, one channel tile per workgroup.
-void dpi_conv_pw_mfma_plan(size_t V, int cout, int* vox_per_block, int* mt) {
+static void pw_mfma_plan(size_t V, int cout, int* vox_per_block, int* mt) {
   int m = cout <= 16 ? 1 : (cout <= 32 ? 2 : 4);
   int vpb = 1024;
   auto waves = [&]() { return (long)cdivz(V, vpb) * (vpb / 256) * cdiv(cout, 16 * m); };
@@ -501,6 +501,13 @@ void dpi_conv_pw_mfma_plan(size_t V, int cout, int* vox_per_block, int* mt) {
   *vox_per_block = vpb;
   *mt = m;
 }
+// one BatchNorm partial row per workgroup column of the forward launch
+int dpi_conv_pw_mfma_stat_blocks(const dpi_conv_desc* d) {
+  const size_t V = (size_t)d->D * d->H * d->W;
+  int vpb, mt;
+  pw_mfma_plan(V, d->Cout, &vpb, &mt);
+  return (int)cdivz(V, vpb);
+}
 
 int dpi_conv_pw_mfma_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y,
                          double* partials, bool flip, int accumulate, hipStream_t st) {
@@ -509,7 +516,7 @@ int dpi_conv_pw_mfma_run(const dpi_conv_desc* d, const float* x, const float* ch
   int vpb, mt;
   PwMArgs a{x, chain, w, bias, y, partials, cin, cout, (size_t)d->D * d->H * d->W, w_out, w_in, accumulate, 0, dpi_io_in(d, flip), dpi_io_out(d, flip), 0};
   a.nt = (g_pw_nt && !accumulate && (size_t)cin * a.V >= ((size_t)32 << 20)) ? 1 : 0;
-  dpi_conv_pw_mfma_plan(a.V, cout, &vpb, &mt);
+  pw_mfma_plan(a.V, cout, &vpb, &mt);
   a.gpb = vpb / 64;
   const unsigned gx = (unsigned)cdivz(a.V, vpb);
   const bool wlds = (long)cdiv(cin, 4) * mt * 64 <= kPwLdsFloats;

@@ -21,9 +21,7 @@
 // w0 + 67, i.e. 18 ALIGNED float4 per row: staged with buffer_load_dwordx4 / ds_write_b128 (W % 4 == 0 makes every float4 lie
 // wholly inside or wholly outside a row; outside -> offset -16 -> the hardware returns 0 = the zero padding).
 // Numerics: fp32 multiply-add chains in (ci, kd, row, kw) order — a plain fp32 direct convolution like the other fp32 kernels.
-#include "common.h"
-
-void dpi_conv_out_dims(const dpi_conv_desc* d, int* Do, int* Ho, int* Wo);
+#include "conv_kernels.h"
 
 namespace {
 
@@ -585,10 +583,11 @@ bool dpi_conv_q4_usable(const dpi_conv_desc* d, bool flip) {
   return tiles >= 192;
 }
 
-int dpi_conv_q4_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
+static int q4_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
   *ntd = cdiv(d->D, 4); *nth = cdiv(d->H, 8); *ntw = cdiv(d->W, 64);
   return *ntd * *nth * *ntw;
 }
+int dpi_conv_q4_stat_blocks(const dpi_conv_desc* d) { int a, b, c; return q4_tiles(d, &a, &b, &c); }
 
 template <int NB, bool FLIP>
 static void q4_launch(const QArgs& a, int ntiles, bool aligned, hipStream_t st) {
@@ -618,7 +617,7 @@ int dpi_conv_q4_run(const dpi_conv_desc* d, const float* x, const float* chain, 
   const int cin = flip ? d->Cout : d->Cin, cout = flip ? d->Cin : d->Cout;
   const long w_out = flip ? 27 : (long)d->Cin * 27, w_in = flip ? (long)d->Cin * 27 : 27;
   QArgs a{x, chain, w, bias, y, partials, cin, cout, d->D, d->H, d->W, 0, 0, 0, w_out, w_in, accumulate, g_q4_dbg};
-  const int ntiles = dpi_conv_q4_tiles(d, &a.ntd, &a.nth, &a.ntw);
+  const int ntiles = q4_tiles(d, &a.ntd, &a.nth, &a.ntw);
   const bool aligned = ((uintptr_t)x & 15) == 0;
   if (cout <= 4) { if (flip) q4_launch<1, true>(a, ntiles, aligned, st); else q4_launch<1, false>(a, ntiles, aligned, st); }
   else { if (flip) q4_launch<2, true>(a, ntiles, aligned, st); else q4_launch<2, false>(a, ntiles, aligned, st); }

@@ -5,11 +5,20 @@
 // limit of the kernels' 32-bit byte offsets, degenerate sizes, every (k, kd, stride, precision) combination, stale descriptor layouts.
 // With no device present a planned launch comes back as DPI_E_LAUNCH from the HIP runtime; everything before it (the code under
 // test) has run under the sanitizers.  Exit code 0 = no sanitizer report and every expectation met.
+//
+// `--dump` prints the planner table instead: for every descriptor of the grid the sizing queries and, for each launcher, the return
+// code and the kernel family that the failed launch names (the text of dpi_last_error() up to its first colon: what follows is the HIP
+// runtime's wording).  A second pass repeats the grid with the MFMA families switched off, which shows the fallback chain.  Per-family
+// counts and a 64-bit digest of the whole table follow; tests/test_host_asan.py pins them.
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 #include <vector>
 #include "../../include/dpi_hip.h"
+#include "../../deep_prior_interpolation_amd/csrc/dpi_hip_internal.h"
 
 static int failures = 0;
 #define EXPECT(cond, ...) do { if (!(cond)) { ++failures; std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
@@ -21,7 +30,74 @@ static dpi_conv_desc desc(int cin, int cout, int D, int H, int W, int k, int kd,
   return d;
 }
 
-int main() {
+static const int channels[][2] = {{64, 4}, {4, 8}, {8, 13}, {25, 16}, {67, 4}, {25, 1}, {25, 25}, {51, 32}, {137, 8}, {105, 64}, {212, 128}, {554, 35},
+                                  {142, 213}, {1, 1}, {3, 5}, {426, 554}, {64, 25}, {67, 25}, {17, 26}};
+static const int shapes[][3] = {{256, 128, 128}, {512, 256, 256}, {128, 64, 64}, {64, 64, 64}, {16, 8, 8}, {4, 4, 4}, {1, 1, 1}, {2, 3, 5}, {9, 17, 33},
+                                {1, 170, 100}, {1, 1, 7}, {33, 31, 50}, {1024, 1024, 256}, {8, 8, 68}, {7, 25, 60}};
+
+// ---- --dump: the planner table ------------------------------------------------------------------------------------------------------
+static uint64_t g_digest = 1469598103934665603ull;      // FNV-1a over every table line, newline included
+static std::map<std::string, long> g_family;            // "pass<n> <launcher> [<text>]" -> count
+static long g_lines = 0;
+static void emit(const dpi_conv_desc& d, int pass, const char* what, const std::string& value) {
+  char id[160];
+  std::snprintf(id, sizeof(id), "pass%d %d->%d %dx%dx%d k%d kd%d s%d p%d io%d ", pass, d.Cin, d.Cout, d.D, d.H, d.W, d.k, d.kd, d.stride, d.precision, d.io);
+  const std::string line = std::string(id) + what + " " + value + "\n";
+  for (unsigned char c : line) { g_digest ^= c; g_digest *= 1099511628211ull; }
+  std::fputs(line.c_str(), stdout);
+  ++g_lines;
+}
+static void emit_rc(const dpi_conv_desc& d, int pass, const char* what, int rc) {
+  std::string text = rc == DPI_OK ? "" : dpi_last_error();
+  if (rc == DPI_E_LAUNCH) text = text.substr(0, text.find(':'));
+  ++g_family["pass" + std::to_string(pass) + " " + what + " [" + text + "]"];
+  emit(d, pass, what, "rc " + std::to_string(rc) + " " + text);
+}
+static void dump_pass(int pass, float* p) {
+  long n_desc = 0;
+  for (auto& ch : channels)
+    for (auto& sh : shapes)
+      for (int k : {1, 3})
+        for (int stride : {1, 2})
+          for (int prec : {0, 1, 2}) {
+            const int kd = sh[0] == 1 ? 1 : k;
+            const int io = (prec < 2 && ((n_desc / 3) & 1)) ? 15 : 0;
+            const dpi_conv_desc d = desc(ch[0], ch[1], sh[0], sh[1], sh[2], k, kd, stride, prec, io);
+            ++n_desc;
+            const size_t fws = dpi_conv_fwd_ws_floats(&d), bws = dpi_conv_bwd_data_ws_floats(&d), wws = dpi_conv_bwd_weight_ws_floats(&d);
+            emit(d, pass, "fwd_stat_blocks", std::to_string(dpi_conv_fwd_stat_blocks(&d)));
+            emit(d, pass, "fwd_ws_floats", std::to_string(fws));
+            emit(d, pass, "bwd_data_ws_floats", std::to_string(bws));
+            emit(d, pass, "bwd_weight_ws_floats", std::to_string(wws));
+            emit_rc(d, pass, "fwd", dpi_conv_fwd(&d, p, nullptr, p, nullptr, p, nullptr, nullptr));
+            emit_rc(d, pass, "bwd_data", dpi_conv_bwd_data(&d, p, p, p, 1, nullptr));
+            // with the workspace the sizing query asks for, the launches that split their input channels say so
+            if (fws) emit_rc(d, pass, "fwd_ws", dpi_conv_fwd_ws(&d, p, nullptr, p, nullptr, p, nullptr, p, fws, nullptr));
+            if (bws) emit_rc(d, pass, "bwd_data_ws", dpi_conv_bwd_data_ws(&d, p, p, p, 1, p, bws, nullptr));
+            if (k == 3 && stride == 1) {
+              const dpi_conv_desc d1 = desc(ch[0], ch[1] + 9, sh[0], sh[1], sh[2], 1, 1, 1, prec);
+              emit_rc(d, pass, "bwd_data_dual", dpi_conv_bwd_data_dual(&d, p, p, &d1, p, p, p, 0, bws ? p : nullptr, bws, nullptr));
+            }
+            emit_rc(d, pass, "bwd_weight", dpi_conv_bwd_weight(&d, p, nullptr, p, p, p, wws, nullptr));
+            // the launch-time facts the backward-weight choice depends on: a chain on x, tensors that are not 16-byte aligned
+            emit_rc(d, pass, "bwd_weight_chained", dpi_conv_bwd_weight(&d, p, p, p, p, p, wws, nullptr));
+            emit_rc(d, pass, "bwd_weight_unaligned", dpi_conv_bwd_weight(&d, p + 1, nullptr, p + 1, p, p, wws, nullptr));
+          }
+}
+static int dump() {
+  std::vector<float> tiny(4, 0.f);
+  dump_pass(0, tiny.data());
+  // the fallback chain: fp32 MFMA, few-output-channel and q4 families off (the library's defaults are restored below)
+  dpi_set_mfma_min_cout(1 << 20); dpi_set_bwd_weight_mfma_min_cout(1 << 20); dpi_set_fewco_mfma(0); dpi_set_q4(0, -1);
+  dump_pass(1, tiny.data());
+  dpi_set_mfma_min_cout(8); dpi_set_bwd_weight_mfma_min_cout(8); dpi_set_fewco_mfma(1); dpi_set_q4(1, -1);
+  for (const auto& kv : g_family) std::printf("count %s %ld\n", kv.first.c_str(), kv.second);
+  std::printf("lines %ld\ndigest %016llx\n", g_lines, (unsigned long long)g_digest);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "--dump") == 0) return dump();
   EXPECT(dpi_version() >= 400, "version %d", dpi_version());
   EXPECT(dpi_conv_desc_size() == (int)sizeof(dpi_conv_desc), "desc size");
   // a buffer that is big enough for the few bytes host code may legitimately read from "device" pointers: none — host code must never
@@ -29,10 +105,6 @@ int main() {
   std::vector<float> tiny(4, 0.f);
   float* p = tiny.data();
   long n_desc = 0, n_planned = 0, n_split = 0;
-  const int channels[][2] = {{64, 4}, {4, 8}, {8, 13}, {25, 16}, {67, 4}, {25, 1}, {25, 25}, {51, 32}, {137, 8}, {105, 64}, {212, 128}, {554, 35},
-                             {142, 213}, {1, 1}, {3, 5}, {426, 554}, {64, 25}, {67, 25}, {17, 26}};
-  const int shapes[][3] = {{256, 128, 128}, {512, 256, 256}, {128, 64, 64}, {64, 64, 64}, {16, 8, 8}, {4, 4, 4}, {1, 1, 1}, {2, 3, 5}, {9, 17, 33},
-                           {1, 170, 100}, {1, 1, 7}, {33, 31, 50}, {1024, 1024, 256}, {8, 8, 68}, {7, 25, 60}};
   for (auto& ch : channels)
     for (auto& sh : shapes)
       for (int k : {1, 3})

@@ -9,9 +9,85 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "deep_prior_interpolation_amd", "csrc")
+EXE = os.path.join(CSRC, "build_asan", "host_asan_driver")
+ENV = dict(ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1", HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs the ROCm compiler")
+
+# `host_asan_driver --dump`: "pass<n> <launcher> [<kernel family the failed launch names, or the error text>]" -> count, the number of table
+# lines and the FNV-1a digest of the table.  pass0 = the library's defaults, pass1 = fp32 MFMA, few-output-channel and q4 families off.
+PLANNER_LINES = 63666
+PLANNER_DIGEST = "13856febc2e2c1fd"
+PLANNER_COUNTS = {
+    "pass0 bwd_data [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass0 bwd_data [conv_bwd_data_s2]": 117,
+    "pass0 bwd_data [conv_bwd_data_s2_mfma]": 630,
+    "pass0 bwd_data [conv_direct]": 67,
+    "pass0 bwd_data [conv_mfma]": 404,
+    "pass0 bwd_data [conv_pw]": 135,
+    "pass0 bwd_data [conv_pw_mfma]": 720,
+    "pass0 bwd_data [conv_q4_mfma]": 32,
+    "pass0 bwd_data [packed-weight scratch]": 460,
+    "pass0 bwd_data_dual [conv_mfma]": 311,
+    "pass0 bwd_data_dual [conv_pw]": 104,
+    "pass0 bwd_data_dual [conv_pw_mfma]": 217,
+    "pass0 bwd_data_dual [packed-weight scratch]": 223,
+    "pass0 bwd_data_ws [conv_mfma (split)]": 50,
+    "pass0 bwd_weight [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass0 bwd_weight [conv_bf16_bwd_weight]": 270,
+    "pass0 bwd_weight [conv_bf16_bww_s2]": 95,
+    "pass0 bwd_weight [conv_bwd_weight]": 571,
+    "pass0 bwd_weight [conv_bwd_weight_mfma]": 971,
+    "pass0 bwd_weight [conv_bwd_weight_smallco]": 28,
+    "pass0 bwd_weight [conv_pw_bwd_weight_mfma]": 630,
+    "pass0 bwd_weight_chained [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass0 bwd_weight_chained [conv_bf16_bwd_weight]": 270,
+    "pass0 bwd_weight_chained [conv_bwd_weight]": 693,
+    "pass0 bwd_weight_chained [conv_bwd_weight_mfma]": 917,
+    "pass0 bwd_weight_chained [conv_bwd_weight_smallco]": 55,
+    "pass0 bwd_weight_chained [conv_pw_bwd_weight_mfma]": 630,
+    "pass0 bwd_weight_unaligned [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass0 bwd_weight_unaligned [conv_bwd_weight]": 687,
+    "pass0 bwd_weight_unaligned [conv_bwd_weight_mfma]": 1209,
+    "pass0 bwd_weight_unaligned [conv_bwd_weight_smallco]": 39,
+    "pass0 bwd_weight_unaligned [conv_pw_bwd_weight_mfma]": 630,
+    "pass0 fwd [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass0 fwd [conv_direct]": 280,
+    "pass0 fwd [conv_fewco_mfma]": 12,
+    "pass0 fwd [conv_mfma]": 858,
+    "pass0 fwd [conv_pw]": 225,
+    "pass0 fwd [conv_pw_mfma]": 630,
+    "pass0 fwd [conv_q4_mfma]": 64,
+    "pass0 fwd [packed-weight scratch]": 496,
+    "pass0 fwd_ws [conv_mfma (split)]": 346,
+    "pass1 bwd_data [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass1 bwd_data [conv_bwd_data_s2]": 747,
+    "pass1 bwd_data [conv_direct]": 503,
+    "pass1 bwd_data [conv_pw]": 855,
+    "pass1 bwd_data [packed-weight scratch]": 460,
+    "pass1 bwd_data_dual [conv_pw]": 632,
+    "pass1 bwd_data_dual [packed-weight scratch]": 223,
+    "pass1 bwd_weight [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass1 bwd_weight [conv_bf16_bwd_weight]": 270,
+    "pass1 bwd_weight [conv_bf16_bww_s2]": 95,
+    "pass1 bwd_weight [conv_bwd_weight]": 2019,
+    "pass1 bwd_weight [conv_bwd_weight_mfma]": 153,
+    "pass1 bwd_weight [conv_bwd_weight_smallco]": 28,
+    "pass1 bwd_weight_chained [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass1 bwd_weight_chained [conv_bf16_bwd_weight]": 270,
+    "pass1 bwd_weight_chained [conv_bwd_weight]": 2240,
+    "pass1 bwd_weight_chained [conv_bwd_weight_smallco]": 55,
+    "pass1 bwd_weight_unaligned [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass1 bwd_weight_unaligned [conv_bwd_weight]": 2331,
+    "pass1 bwd_weight_unaligned [conv_bwd_weight_mfma]": 195,
+    "pass1 bwd_weight_unaligned [conv_bwd_weight_smallco]": 39,
+    "pass1 fwd [conv: 1x1 convolution supports stride 1 only]": 855,
+    "pass1 fwd [conv_direct]": 1214,
+    "pass1 fwd [conv_pw]": 855,
+    "pass1 fwd [packed-weight scratch]": 496,
+}
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs the ROCm compiler")
+@needs_hipcc
 def test_host_logic_under_asan_and_ubsan():
     """Descriptor validation, launch planning and workspace sizing of every conv entry point over ~3400 edge-case descriptors
     (bench patch, field-scale patch, 2^29-voxel limit, degenerate sizes, stale layouts), with AddressSanitizer and
@@ -23,3 +99,28 @@ def test_host_logic_under_asan_and_ubsan():
                                 HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES=""))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@needs_hipcc
+def test_planner_table_is_pinned():
+    """Which kernel family every descriptor of the driver's grid gets (forward, backward-data, the fused pair, backward-weight with and
+    without a chain / aligned tensors), the BatchNorm partial rows and the three workspace sizes: the counts per family and the digest of
+    the whole table are those of the commit BEFORE the launch planners (conv_plan, bw_plan) were introduced, so the planners provably
+    choose and size as the hand-copied chains did.  A host without a device fails every planned launch in dpi_check_launch, and the error
+    text names the family.
+
+    When a later change alters a choice or a size ON PURPOSE: build the sanitizer driver (`make -C deep_prior_interpolation_amd/csrc
+    asan`), run `HIP_VISIBLE_DEVICES= ROCR_VISIBLE_DEVICES= build_asan/host_asan_driver --dump` with no DPI_* variable set, diff the table
+    against the one of the parent commit (its csrc/ objects link with this driver.cpp too: only the public ABI and the hidden setters are
+    used) to see that exactly the intended lines moved, then copy the `count`, `lines` and `digest` lines at its end into the constants
+    above."""
+    subprocess.check_call(["make", "-C", CSRC, "-j4", "asan"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DPI_")}      # the getenv knobs of the planners stay at their defaults
+    r = subprocess.run([EXE, "--dump"], capture_output=True, text=True, timeout=300, env=dict(env, **ENV))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    tail = [ln for ln in r.stdout.splitlines() if ln.startswith(("count ", "lines ", "digest "))]
+    counts = {ln[6:].rsplit(" ", 1)[0]: int(ln.rsplit(" ", 1)[1]) for ln in tail if ln.startswith("count ")}
+    assert counts == PLANNER_COUNTS, sorted(set(counts.items()) ^ set(PLANNER_COUNTS.items()))
+    assert "lines %d" % PLANNER_LINES in tail
+    assert "digest " + PLANNER_DIGEST in tail
