@@ -120,6 +120,9 @@ __device__ __forceinline__ float4 dpi_ld4_raw_bf16(const float* base, size_t i) 
   const unsigned u0 = u.x, u1 = u.y;
   return make_float4(__builtin_bit_cast(float, u0), __builtin_bit_cast(float, u1), 0.f, 0.f);
 }
+// whether dpi_ld4 / dpi_ld4_raw_bf16 / dpi_st4 may be used on a tensor: its base on 16 bytes (fp32) / 8 bytes (bf16).  A kernel that is a
+// fall-back for unaligned views takes its vector path only where this holds as well as its shape condition (wave-uniform).
+__device__ __forceinline__ bool dpi_vec4_base(const void* base, bool bf) { return (reinterpret_cast<uintptr_t>(base) & (bf ? 7u : 15u)) == 0; }
 // four consecutive elements starting at element i (i % 4 == 0 and an aligned base: 16-byte / 8-byte accesses)
 __device__ __forceinline__ float4 dpi_ld4(const float* base, size_t i, bool bf, bool nt) {
   if (bf) {

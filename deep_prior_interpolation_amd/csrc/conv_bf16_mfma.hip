@@ -1146,7 +1146,10 @@ int dpi_conv_bf16_run(const dpi_conv_desc* d, const float* x, const float* chain
   }
   BArgs a{x, chain, w, bias, y, partials, cin, cout, d->D, d->H, d->W, 0, 0, 0, 0, w_out, w_in, wpk, accumulate, g_bf16_debug,
           dpi_io_in(d, flip), dpi_io_out(d, flip), nullptr, nullptr, 0, 0, 0};
-  if (a.xb && (((uintptr_t)x & 7) || (sec && ((uintptr_t)sec->x2 & 7)))) { dpi_set_error("conv_bf16_mfma: a bf16 input tensor must be 8-byte aligned"); return DPI_E_ARG; }
+  if (a.xb && (((uintptr_t)x & 7) || (sec && ((uintptr_t)sec->x2 & 7)))) {     // named as the caller's entry point names them
+    dpi_set_error("conv_bf16_mfma: the bf16 input tensor %s must be 8-byte aligned", ((uintptr_t)x & 7) ? (flip ? "dy" : "x") : "dy1");
+    return DPI_E_ARG;
+  }
   if (sec) { a.x2 = sec->x2; a.w2 = sec->w2; a.C2 = sec->C2; a.w2_co_stride = sec->w2_co_stride; a.w2_c_stride = sec->w2_c_stride; }
   const int ntiles = bf16_tiles(d, nr, nh, &a.ntd, &a.nth, &a.ntw);
   a.ny = cdiv(cout, 16 * mt);
@@ -1175,7 +1178,7 @@ static int bf16_s2_tiles(const dpi_conv_desc* d, int* ntd, int* nth, int* ntw) {
 int dpi_conv_bf16_s2_stat_blocks(const dpi_conv_desc* d) { int a, b, c; return bf16_s2_tiles(d, &a, &b, &c); }
 int dpi_conv_bf16_s2_run(const dpi_conv_desc* d, const float* x, const float* chain, const float* w, const float* bias, float* y, double* partials,
                          hipStream_t st) {
-  if ((uintptr_t)x & 7) { dpi_set_error("conv_bf16_s2: a bf16 input tensor must be 8-byte aligned"); return DPI_E_ARG; }
+  if ((uintptr_t)x & 7) { dpi_set_error("conv_bf16_s2: the bf16 input tensor x must be 8-byte aligned"); return DPI_E_ARG; }
   const int mt = d->Cout > 32 ? 4 : (d->Cout > 16 ? 2 : 1);
   const int cout_pad = cdiv(d->Cout, 16 * mt) * mt;            // 16-channel tiles written by the pack kernel
   unsigned short* const wpk = static_cast<unsigned short*>(dpi_pack_slot(w, 3, d->Cin, d->Cout, 32 | (mt << 6),

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(BwArgs a) {
   const int ci0 = blockIdx.y * CI_B, co_base = blockIdx.z * CO_B;
   const int my_ci = ci0 + wid;
   const size_t V = (size_t)a.D * a.H * a.W, Vo = (size_t)a.Do * a.Ho * a.Wo;
-  const bool wo_vec = (OW == 4) && ((a.Wo & 3) == 0);
+  const bool wo_vec = (OW == 4) && ((a.Wo & 3) == 0) && dpi_vec4_base(a.dy, a.dyb != 0);   // else: a view moved off its 16 / 8 bytes
 
   float acc[CO_B][TAPS];
 #pragma unroll
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_pw_kernel(BwPwArgs a) {
     for (int o = 0; o < CO_B; ++o) acc[i][o] = 0.f;
   const size_t vbeg = (size_t)blockIdx.x * a.vox_per_chunk;
   const size_t vend = vbeg + a.vox_per_chunk < a.V ? vbeg + a.vox_per_chunk : a.V;
-  const bool vec = (a.V & 3) == 0;
+  const bool vec = (a.V & 3) == 0 && dpi_vec4_base(a.x, a.xb != 0) && dpi_vec4_base(a.dy, a.dyb != 0);
   for (size_t v0 = vbeg + (size_t)tid * 4; v0 < vend; v0 += 1024) {
     float xi[CI_B][4], g[CO_B][4];
 #pragma unroll

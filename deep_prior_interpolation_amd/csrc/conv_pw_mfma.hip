@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void conv_pw_bwd_weight_mfma_kernel(PwBwArgs a
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int lk = lane >> 4, lj = lane & 15;
   const int ci0 = blockIdx.y * 16 * NT, co0 = blockIdx.z * 16 * MT;
-  const bool vec = (a.V & 3) == 0;
+  const bool vec = (a.V & 3) == 0 && dpi_vec4_base(a.x, XB) && dpi_vec4_base(a.dy, DYB);   // the fall-back for unaligned views, too
   f32x4 acc[MT][NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)

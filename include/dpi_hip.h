@@ -24,6 +24,25 @@
  *    NULL = identity.
  *  - "stat partials": double[nblk][C][2] = per-block {sum, sum of squares}; reduced in fixed order by
  *    dpi_bn_finalize (deterministic, double precision).
+ *  - Alignment and extent (what tests/test_gpu_conv_contract.py holds every convolution launch to, inside guard bands):
+ *    a tensor is a channel slice of an allocation whose base is 16-byte aligned.  With a voxel count that is no multiple of 4 such a
+ *    slice has the alignment of its ELEMENT only — 4 bytes for fp32, 2 bytes for a bf16 tensor (dpi_conv_desc.io) — and every entry
+ *    point takes such a slice.  A view moved off the alignment its slice would have is served only by the kernels listed next, and is
+ *    neither served nor refused by the others (gating those on the address as well is open work).  Launch variants that need more (16-byte staging loads, 8-byte / dword stores of two elements) are chosen from the
+ *    addresses of the call as well as from the shape, and have an element-wise twin; results of the variants agree to rounding.
+ *    Chosen that way, so that a view moved off its natural alignment (by any number of elements) is served too: every kernel of
+ *    dpi_conv_bwd_weight, the 3x3(x3) MFMA kernels of dpi_conv_fwd / dpi_conv_bwd_data (fp32 arithmetic, both strides, the 4x4x1
+ *    kernel included), stride-2 dpi_conv_bwd_data, dpi_upsample2x_bwd and dpi_hale_sections.  The other kernels (1x1x1 and VALU
+ *    forward / backward-data, the element-wise operators) vectorise where the voxel count (the output row, for the VALU stencil) is a
+ *    multiple of 4 and rely on what a channel slice then has: 16 bytes for fp32, 8 bytes for bf16.
+ *    Refused with DPI_E_ARG, before anything that touches the caller's buffers is launched ("... the bf16 input tensor <name> must be
+ *    8-byte aligned", <name> = x, dy or dy1): a bf16 INPUT (x of dpi_conv_fwd, dy / dy3 / dy1 of dpi_conv_bwd_data / _dual) that is not
+ *    8-byte aligned when the launch belongs to the bf16 stencil kernels, i.e. precision >= 1, 3x3(x3), stride 1 with W % 4 == 0, or
+ *    precision 1, 3x3x3, stride 2, bf16 x and y with W % 4 == 0.  Workspaces, weights, chains and statistic partials are the caller's own
+ *    allocations: 16-byte aligned (any allocator's base address is).
+ *    A launch writes its output tensor and nothing else of the caller's: `stat_partials` receives exactly
+ *    dpi_conv_fwd_stat_blocks(d) rows of Cout x 2 doubles, every one of them written; a workspace is used up to at most the floats its
+ *    sizing query names (dpi_conv_*_ws_floats), for every chain / alignment a launch of that descriptor can have.
  */
 #ifndef DPI_HIP_H
 #define DPI_HIP_H

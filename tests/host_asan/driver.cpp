@@ -10,6 +10,7 @@
 // code and the kernel family that the failed launch names (the text of dpi_last_error() up to its first colon: what follows is the HIP
 // runtime's wording).  A second pass repeats the grid with the MFMA families switched off, which shows the fallback chain.  Per-family
 // counts and a 64-bit digest of the whole table follow; tests/test_host_asan.py pins them.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -96,8 +97,80 @@ static int dump() {
   return 0;
 }
 
+// ---- --plan: the planner's answers for descriptor rows read from stdin -----------------------------------------------------------------
+// One row per line (tests/conv_contract_cases.py writes them):
+//   <launcher> <Cin> <Cout> <C1> <D> <H> <W> <k> <kd> <stride> <precision> <io> <key>=<value>,... | -
+// launcher = fwd | bwd_data | bwd_data_dual | bwd_weight; C1 = output channels of the 1x1(x1) layer of bwd_data_dual (0 elsewhere); the
+// last field lists dpi_set_option keys that hold for this row only (they reach the hidden setters through dpi_set_option's table; the
+// library's defaults are restored after the row).  Printed per row: "plan <row> <what> <value>" with the three size queries and, for every
+// launch the launcher's device test makes, "<launch> [<family>]" — the family exactly as emit_rc derives it.
+// The first line, "defaults <key>=<value>,...", names the knobs the library starts with (tests/conv_contract_cases.py holds them).
+// Applies such a list; returns the token that dpi_set_option refused, or nullptr.
+static const char* set_options(const std::string& list) {
+  static std::string bad;
+  if (list == "-") return nullptr;
+  for (size_t at = 0; at < list.size();) {
+    const size_t end = std::min(list.find(',', at), list.size()), eq = list.find('=', at);
+    bad = list.substr(at, end - at);
+    if (eq == std::string::npos || eq >= end) return bad.c_str();
+    if (dpi_set_option(list.substr(at, eq - at).c_str(), std::atoi(list.c_str() + eq + 1)) != DPI_OK) return bad.c_str();
+    at = end + 1;
+  }
+  return nullptr;
+}
+static std::string family_of(int rc) {
+  std::string text = rc == DPI_OK ? "" : dpi_last_error();
+  if (rc == DPI_E_LAUNCH) text = text.substr(0, text.find(':'));
+  return "[" + text + "]";
+}
+static int plan() {
+  std::vector<float> tiny(4, 0.f);
+  float* p = tiny.data();
+  char line[1024], defaults[768];
+  if (!std::fgets(line, sizeof(line), stdin) || std::sscanf(line, "defaults %767s", defaults) != 1 || set_options(defaults)) {
+    std::printf("plan error: the first line must be 'defaults <key>=<value>,...'\n");
+    return 2;
+  }
+  long row = 0;
+  for (; std::fgets(line, sizeof(line), stdin); ++row) {
+    char launcher[32], opts[768];
+    int cin, cout, c1, D, H, W, k, kd, stride, prec, io;
+    if (std::sscanf(line, "%31s %d %d %d %d %d %d %d %d %d %d %d %767s", launcher, &cin, &cout, &c1, &D, &H, &W, &k, &kd, &stride, &prec, &io, opts) != 13) {
+      std::printf("plan %ld error malformed row\n", row);
+      return 2;
+    }
+    if (const char* bad = set_options(opts)) { std::printf("plan %ld error bad option %s\n", row, bad); return 2; }
+    const dpi_conv_desc d = desc(cin, cout, D, H, W, k, kd, stride, prec, io);
+    const size_t fws = dpi_conv_fwd_ws_floats(&d), bws = dpi_conv_bwd_data_ws_floats(&d), wws = dpi_conv_bwd_weight_ws_floats(&d);
+    std::printf("plan %ld fwd_stat_blocks %d\nplan %ld fwd_ws_floats %zu\nplan %ld bwd_data_ws_floats %zu\nplan %ld bwd_weight_ws_floats %zu\n",
+                row, dpi_conv_fwd_stat_blocks(&d), row, fws, row, bws, row, wws);
+    const std::string what = launcher;
+    if (what == "fwd") {
+      std::printf("plan %ld fwd %s\n", row, family_of(dpi_conv_fwd(&d, p, nullptr, p, nullptr, p, nullptr, nullptr)).c_str());
+      if (fws) std::printf("plan %ld fwd_ws %s\n", row, family_of(dpi_conv_fwd_ws(&d, p, nullptr, p, nullptr, p, nullptr, p, fws, nullptr)).c_str());
+    } else if (what == "bwd_data") {
+      std::printf("plan %ld bwd_data %s\n", row, family_of(dpi_conv_bwd_data(&d, p, p, p, 1, nullptr)).c_str());
+      if (bws) std::printf("plan %ld bwd_data_ws %s\n", row, family_of(dpi_conv_bwd_data_ws(&d, p, p, p, 1, p, bws, nullptr)).c_str());
+    } else if (what == "bwd_data_dual") {
+      const dpi_conv_desc d1 = desc(cin, c1, D, H, W, 1, 1, 1, prec, io);
+      std::printf("plan %ld bwd_data_dual %s\n", row, family_of(dpi_conv_bwd_data_dual(&d, p, p, &d1, p, p, p, 0, bws ? p : nullptr, bws, nullptr)).c_str());
+    } else if (what == "bwd_weight") {
+      std::printf("plan %ld bwd_weight %s\n", row, family_of(dpi_conv_bwd_weight(&d, p, nullptr, p, p, p, wws, nullptr)).c_str());
+      std::printf("plan %ld bwd_weight_chained %s\n", row, family_of(dpi_conv_bwd_weight(&d, p, p, p, p, p, wws, nullptr)).c_str());
+      std::printf("plan %ld bwd_weight_unaligned %s\n", row, family_of(dpi_conv_bwd_weight(&d, p + 1, nullptr, p + 1, p, p, wws, nullptr)).c_str());
+    } else {
+      std::printf("plan %ld error unknown launcher %s\n", row, launcher);
+      return 2;
+    }
+    set_options(defaults);
+  }
+  std::printf("rows %ld\n", row);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::strcmp(argv[1], "--dump") == 0) return dump();
+  if (argc > 1 && std::strcmp(argv[1], "--plan") == 0) return plan();
   EXPECT(dpi_version() >= 400, "version %d", dpi_version());
   EXPECT(dpi_conv_desc_size() == (int)sizeof(dpi_conv_desc), "desc size");
   // a buffer that is big enough for the few bytes host code may legitimately read from "device" pointers: none — host code must never

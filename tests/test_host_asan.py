@@ -124,3 +124,39 @@ def test_planner_table_is_pinned():
     assert counts == PLANNER_COUNTS, sorted(set(counts.items()) ^ set(PLANNER_COUNTS.items()))
     assert "lines %d" % PLANNER_LINES in tail
     assert "digest " + PLANNER_DIGEST in tail
+
+
+@needs_hipcc
+def test_contract_cases_cover_the_planner():
+    """tests/conv_contract_cases.py — the rows tests/test_gpu_conv_contract.py launches on a device — against the planner itself
+    (`host_asan_driver --plan`: each row's family as the failed launch names it, under the row's own knobs):
+     (1) every row reaches the family the table claims for each of its launches, and the row ids are unique;
+     (2) every kernel family of PLANNER_COUNTS — every bracketed text that names a kernel, for every launcher, in both passes — is
+         reached by at least one row that runs under that pass's knobs.  Not kernels: the `conv: ...` argument errors and
+         `packed-weight scratch`, which is what the bf16 stencil kernels answer without a device (the table has rows for them too).
+    The driver cannot see the variants a family chooses from a pointer's address (vectorised staging, pair / float2 epilogues, the
+    aligned q4 kernel, ...): the error text names the family only.  Their coverage rests on the shape conditions read from the code and
+    stated next to each row of ADDRESS_CASES in the device test."""
+    import collections
+    import conv_contract_cases as T
+    ids = [T.case_id(c) for c in T.CASES]
+    assert len(set(ids)) == len(ids), [i for i, n in collections.Counter(ids).items() if n > 1]
+    subprocess.check_call(["make", "-C", CSRC, "-j4", "asan"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DPI_")}
+    r = subprocess.run([EXE, "--plan"], input=T.plan_input(env), capture_output=True, text=True, timeout=300, env=dict(env, **ENV))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    assert "rows %d" % len(T.CASES) in r.stdout.splitlines()
+    got = collections.defaultdict(dict)
+    for ln in r.stdout.splitlines():
+        f = ln.split(" ", 3)
+        if f[0] == "plan" and f[3].startswith("["):
+            got[int(f[1])][f[2]] = f[3][1:-1]
+    reached = set()
+    for i, c in enumerate(T.CASES):
+        assert got[i] == c.reaches, (ids[i], got[i], c.reaches)
+        if T.planner_pass(c) is not None:
+            reached.update("pass%d %s [%s]" % (T.planner_pass(c), launch, family) for launch, family in got[i].items())
+    kernels = {k for k in PLANNER_COUNTS if "[conv: " not in k and "[packed-weight scratch]" not in k}
+    assert len(kernels) == 50
+    assert not kernels - reached, sorted(kernels - reached)
