@@ -88,6 +88,9 @@ SIGNATURES = {
     "dpi_loss_ws_doubles": (_Z, [_Z]),
     "dpi_masked_loss": (_I, [_P, _P, _P, _Z, _I, _F, _P, _P, _P, _P]),
     "dpi_adam_multi": (_I, [_P, _P, _I, _P, C.c_double, C.c_double, C.c_double, _P, _P]),
+    # --optimizer sgld | psgld: (table, sizes, ntensors, step_lr, kind, weight_decay, beta, lambda, noise_scale, temperature, seed, xi, active, stream)
+    "dpi_langevin_multi": (_I, [_P, _P, _I, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _U64, _P, _P, _P]),
+    "dpi_moments_update": (_I, [_P, _P, _P, _Z, _P, _I, _I, _P, _P]),
     "dpi_loop_control": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, C.c_double, C.c_double, _I, C.c_double, _P]),
     "dpi_copy_if": (_I, [_P, _P, _P, _Z, _P]),
     "dpi_masked_loss_holdout": (_I, [_P, _P, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P]),     # ABI 406: --holdout

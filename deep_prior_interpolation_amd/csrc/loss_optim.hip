@@ -204,6 +204,111 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ zi
   }
 }
 
+// ---- Langevin samplers (--optimizer sgld | psgld) ---------------------------------------------------------------
+// One element of the reference's SGLD.step (optimizers.py:79-106, momentum 0) / pSGLD.step (optimizers.py:144-181, not centred), with
+// the rounding points of the torch CPU calls it makes: Tensor.add_(alpha, other) is ONE fused multiply-add (other * alpha + self),
+// addcmul_(value, a, b) is fma(value * a, b, self), addcdiv_(value, a, b) is self + (value * a) / b, and `2*lr / G` is
+// G.reciprocal() * (2*lr).  The library is built with -ffp-contract=off: only the fmaf() below fuse.  sqrt_temp = sqrt(temperature)
+// multiplies last (xi itself for SGLD, whose noise add is the fused one), so temperature 1 multiplies by exactly 1.
+struct LangevinScalars { int kind, has_wd; float wd, neg_lr, beta, omb, lam, two_lr, sqrt_ns, sqrt_temp; };
+__device__ __forceinline__ void langevin_element(const LangevinScalars& s, float& p, float g, float& V, float xi) {
+  const float d = s.has_wd ? fmaf(p, s.wd, g) : g;                 // weight decay: an add with alpha (fused)
+  if (s.kind == 0) {
+    p = fmaf(d, s.neg_lr, p);                                      // drift: an add with alpha = -lr (fused)
+    p = fmaf(xi * s.sqrt_temp, s.sqrt_ns, p);                      // noise: an add with alpha = sqrt(noise_scale) (fused)
+  } else {
+    V = fmaf(s.omb * d, d, V * s.beta);                            // mul by beta, then addcmul with value 1 - beta
+    const float G = sqrtf(V) + s.lam;                              // sqrt, then add Lambda
+    p = p + (s.neg_lr * d) / G;                                    // drift: addcdiv with value -lr
+    const float ns = sqrtf((1.f / G) * s.two_lr);                  // noise std: reciprocal of G times 2 lr, then sqrt
+    p = p + (xi * ns) * s.sqrt_temp;                               // noise: product first, then a plain add
+  }
+}
+
+// Grid, table and step_lr as adam_kernel.  xi == NULL: the normals come from Philox — key `seed`, stream id (0xFFFFFFFE << 32) | step,
+// counter (row << 40) | q with q the group of four elements inside the tensor; else xi[row] holds them (parity mode).
+// 16-byte accesses only on rows whose pointers are all 16-byte aligned (the state slices start at arbitrary element offsets).
+__global__ __launch_bounds__(256) void langevin_kernel(const dpi_adam_tensor* __restrict__ tensors, const int64_t* __restrict__ sizes,
+                                                       const float* __restrict__ step_lr, int kind, double wdd, double betad, double lambdad,
+                                                       double noise_scaled, float sqrt_temp, uint64_t seed, const float* const* __restrict__ xi,
+                                                       const int* __restrict__ active) {
+  if (active && *active == 0) return;
+  const dpi_adam_tensor t = tensors[blockIdx.y];
+  const size_t n = (size_t)sizes[blockIdx.y];
+  const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  // scalars as the reference's Python derives them: in double, then rounded to fp32 where torch takes them as the alpha / value of an op
+  const float lr = step_lr[1];
+  LangevinScalars s;
+  s.kind = kind; s.has_wd = wdd != 0.0; s.wd = (float)wdd; s.neg_lr = -lr;
+  s.beta = (float)betad; s.omb = (float)(1.0 - betad); s.lam = (float)lambdad; s.two_lr = 2.f * lr;
+  s.sqrt_ns = (float)sqrt(noise_scaled); s.sqrt_temp = sqrt_temp;
+  const uint64_t sid = (0xFFFFFFFEull << 32) | (uint64_t)(uint32_t)step_lr[0];
+  const uint64_t row = (uint64_t)blockIdx.y << 40;
+  const float* __restrict__ x = xi ? xi[blockIdx.y] : nullptr;
+  const bool vec = dpi_vec4_base(t.p, false) && dpi_vec4_base(t.g, false) && (kind == 0 || dpi_vec4_base(t.v, false)) &&
+                   (!x || dpi_vec4_base(x, false));
+  for (size_t i = i0; i < n; i += (size_t)gridDim.x * 1024) {
+    float z[4];
+    if (!x) philox4(row | (uint64_t)(i >> 2), sid, seed, z);
+    if (vec && i + 4 <= n) {
+      float4 p4 = dpi_ld4(t.p, i, false, false);
+      const float4 g4 = dpi_ld4(t.g, i, false, false);
+      float4 v4 = kind == 1 ? dpi_ld4(t.v, i, false, false) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (x) { const float4 x4 = dpi_ld4(x, i, false, false); z[0] = x4.x; z[1] = x4.y; z[2] = x4.z; z[3] = x4.w; }
+      langevin_element(s, p4.x, g4.x, v4.x, z[0]);
+      langevin_element(s, p4.y, g4.y, v4.y, z[1]);
+      langevin_element(s, p4.z, g4.z, v4.z, z[2]);
+      langevin_element(s, p4.w, g4.w, v4.w, z[3]);
+      if (kind == 1) dpi_st4(t.v, i, v4, false, false);
+      dpi_st4(t.p, i, p4, false, false);
+    } else {
+      for (int k = 0; k < 4 && i + k < n; ++k) {
+        float p = t.p[i + k], V = kind == 1 ? t.v[i + k] : 0.f;
+        langevin_element(s, p, t.g[i + k], V, x ? x[i + k] : z[k]);
+        if (kind == 1) t.v[i + k] = V;
+        t.p[i + k] = p;
+      }
+    }
+  }
+}
+
+// ---- posterior moments: Welford running mean and sum of squared deviations of the net output over the sampled iterations -----------
+// it = step_lr[0] = the 0-based iteration index when launched before the optimiser step.  Every element is owned by one thread and the
+// sample number k is a pure function of `it`: no block reads what another wrote.
+__global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ out, float* __restrict__ mean, float* __restrict__ m2,
+                                                      size_t n, const float* __restrict__ step_lr, int burn_in, int thin,
+                                                      const int* __restrict__ active) {
+  if (active && *active == 0) return;
+  const int it = (int)step_lr[0];
+  if (it < burn_in || (it - burn_in) % thin != 0) return;
+  const float k = (float)((it - burn_in) / thin + 1);
+  const bool vec = (n & 3) == 0 && dpi_vec4_base(out, false) && dpi_vec4_base(mean, false) && dpi_vec4_base(m2, false);
+  const bool nt = n >= ((size_t)32 << 20);          // streaming tensors beyond the Infinity Cache: non-temporal accesses (noise_kernel)
+  if (vec) {
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 1024) {
+      const float4 x = dpi_ld4(out, i, false, nt);
+      float4 m = dpi_ld4(mean, i, false, nt), q = dpi_ld4(m2, i, false, nt);
+      float d;
+      d = x.x - m.x; m.x += d / k; q.x += d * (x.x - m.x);
+      d = x.y - m.y; m.y += d / k; q.y += d * (x.y - m.y);
+      d = x.z - m.z; m.z += d / k; q.z += d * (x.z - m.z);
+      d = x.w - m.w; m.w += d / k; q.w += d * (x.w - m.w);
+      dpi_st4(mean, i, m, false, nt);
+      dpi_st4(m2, i, q, false, nt);
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+      const float x = out[i];
+      float m = mean[i];
+      const float d = x - m;
+      m += d / k;
+      mean[i] = m;
+      m2[i] += d * (x - m);
+    }
+  }
+}
+
 // ---- overlap-add -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restrict__ patch, int pd, int ph, int pw, int od, int oh, int ow,
                                                           float* __restrict__ acc, int D, int H, int W) {
@@ -360,6 +465,26 @@ extern "C" int dpi_adam_multi(const dpi_adam_tensor* tensors, const int64_t* siz
   // grid.x is sized for the largest tensor by the caller-independent cap below; blocks past a tensor's end exit.
   adam_kernel<<<dim3(256, ntensors), 256, 0, (hipStream_t)stream>>>(tensors, sizes, step_lr, beta1, beta2, eps, active);
   return dpi_check_launch("adam_multi");
+}
+
+extern "C" int dpi_langevin_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors, const float* step_lr, int kind,
+                                  double weight_decay, double beta, double lambda, double noise_scale, double temperature, uint64_t seed,
+                                  const float* const* xi, const int* active, void* stream) {
+  DPI_REQUIRE(tensors && sizes && step_lr && ntensors > 0 && ntensors <= 65535, "langevin_multi: bad argument");
+  DPI_REQUIRE(kind == 0 || kind == 1, "langevin_multi: kind must be 0 (SGLD) or 1 (pSGLD)");
+  DPI_REQUIRE(temperature >= 0.0 && noise_scale >= 0.0 && lambda >= 0.0 && weight_decay >= 0.0,
+              "langevin_multi: temperature, noise_scale, lambda and weight_decay must be >= 0");
+  langevin_kernel<<<dim3(256, ntensors), 256, 0, (hipStream_t)stream>>>(tensors, sizes, step_lr, kind, weight_decay, beta, lambda, noise_scale,
+                                                                        (float)sqrt(temperature), seed, xi, active);
+  return dpi_check_launch("langevin_multi");
+}
+
+extern "C" int dpi_moments_update(const float* out, float* mean, float* m2, size_t n, const float* step_lr, int burn_in, int thin,
+                                  const int* active, void* stream) {
+  DPI_REQUIRE(out && mean && m2 && step_lr && n > 0, "moments_update: bad argument");
+  DPI_REQUIRE(thin >= 1 && burn_in >= 0, "moments_update: burn_in must be >= 0 and thin >= 1");
+  moments_kernel<<<nblocks(cdivz(n, 4)), 256, 0, (hipStream_t)stream>>>(out, mean, m2, n, step_lr, burn_in, thin, active);
+  return dpi_check_launch("moments_update");
 }
 
 extern "C" int dpi_noise_add_io(const float* z, size_t n, float std, uint64_t seed, const uint64_t* step_ptr, float* out, unsigned io,

@@ -15,7 +15,7 @@ from . import _lib, ops
 from . import utils as u
 from .architectures import get_net
 from .data import extract_patches
-from .optim import DevicePlateau, FusedAdam
+from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
 from .parameter import net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
@@ -41,6 +41,15 @@ class Interpolator:
             raise ValueError("--holdout must lie in [0, 0.5], got %r" % self.holdout)
         self.holdout_sel = self._holdout_dev = None              # per-trace selection: numpy (patch order without t) / device (C, S...)
         self.best_iter = self.val_min = None
+        # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
+        self.optimizer_kind = getattr(args, "optimizer", "adam")
+        if self.optimizer_kind not in ("adam", "sgld", "psgld"):
+            raise ValueError("--optimizer must be adam, sgld or psgld, got %r" % (self.optimizer_kind,))
+        burn = getattr(args, "posterior_burnin", None)
+        self.posterior_burnin = int(args.epochs) // 2 if burn is None else int(burn)
+        self.posterior_thin = int(getattr(args, "posterior_thin", None) or 1)
+        self._post_mean = self._post_m2 = None                   # Welford buffers of the patch (dpi_moments_update)
+        self._reset_posterior()
         self.history = self._new_history()
         self.image_name = None
         self.img = self.img_ = self.mask = self.mask_ = None
@@ -70,6 +79,7 @@ class Interpolator:
         self._patches_seen = 0
         self._noise_step.zero_()
         self.holdout_sel = self._holdout_dev = None              # drawn again from the new seed (build_holdout)
+        self._zero_moments()
 
     def load_data(self, data):
         """(T,X,Y,C) numpy patch -> (1,C,T,X,Y) fp32 device tensors; returns std of the masked data (main.py:118-139)."""
@@ -98,6 +108,89 @@ class Interpolator:
     def _ensure_holdout(self):
         if self.holdout > 0.0 and self._holdout_dev is None:
             self.build_holdout()
+
+    # ---- Langevin sampling (--optimizer sgld | psgld) ---------------------------------------------------------
+    def is_sampler(self):
+        return self.optimizer_kind != "adam"
+
+    def _reset_posterior(self):
+        self.posterior_std = self.output_selected = self.posterior_samples = self.posterior_snr = self.posterior_val_snr = None
+
+    def _zero_moments(self):
+        if self._post_mean is not None:
+            self._post_mean.zero_()
+            self._post_m2.zero_()
+
+    def langevin_temperature(self):
+        """--langevin_temperature, or 1/N with N the number of samples the loss averages over (the non-zeros of the patch's training
+        mask): the reference's noise rule belongs to a SUMMED misfit, our loss is its mean, so temperature 1 over-heats the chain N-fold."""
+        t = getattr(self.args, "langevin_temperature", None)
+        if t is not None:
+            return float(t)
+        n = int(torch.count_nonzero(self.training_mask()).item())
+        return 1.0 / n if n > 0 else 1.0
+
+    def make_optimizer(self):
+        """The optimiser of one patch: FusedAdam, or the Langevin sampler --optimizer names, keyed by the patch seed (its noise does not
+        depend on rank or slot).  A new optimiser starts a new chain: the posterior moments of the patch start from zero."""
+        a = self.args
+        self._reset_posterior()
+        self._zero_moments()
+        if not self.is_sampler():
+            return FusedAdam(self.net.parameters(), lr=a.lr)
+        return FusedLangevin(self.net.parameters(), self.optimizer_kind, lr=a.lr, weight_decay=float(getattr(a, "weight_decay", 0.0)),
+                             beta=float(getattr(a, "psgld_beta", 0.99)), Lambda=float(getattr(a, "psgld_lambda", 1e-8)),
+                             noise_scale=float(getattr(a, "sgld_noise_scale", 0.1)), temperature=self.langevin_temperature(),
+                             seed=self.noise_seed, noise="torch_cpu" if self.noise_source() == "torch_cpu" else "philox")
+
+    def _moments_update(self, out_):
+        """Fold the output of this iteration into the running mean / m2 when the iteration is a sampled one (decided on the device from the
+        optimiser's step counter: call before optimizer.step())."""
+        o = out_.detach()
+        if o.dtype != torch.float32 or not o.is_contiguous():
+            o = o.float().contiguous()
+        if self._post_mean is None or self._post_mean.shape != o.shape:
+            self._post_mean, self._post_m2 = torch.zeros_like(o), torch.zeros_like(o)
+        opt = self.optimizer
+        _lib.check(_lib.load().dpi_moments_update(_lib.ptr(o), _lib.ptr(self._post_mean), _lib.ptr(self._post_m2), o.numel(),
+                                                  _lib.ptr(opt.step_lr), self.posterior_burnin, self.posterior_thin, _lib.ptr(opt.active),
+                                                  _lib.stream()), "dpi_moments_update")
+
+    def _finish_posterior(self):
+        """After the loop of a sampler run (eager and graph): out_best becomes the posterior mean over the K sampled iterations, the
+        loss- / holdout-selected iterate stays available as output_selected, posterior_std = sqrt(m2 / (K - 1)); one more loss pass on the
+        mean gives its SNR (and, with --holdout, its held-out SNR)."""
+        if not self.is_sampler():
+            return
+        self._reset_posterior()
+        K = posterior_sample_count(self.iiter, self.posterior_burnin, self.posterior_thin)
+        self.output_selected = self.out_best
+        if K < 1:
+            return
+        self.posterior_samples = K
+        mean = self._post_mean.clone()
+        self._out_best_dev = mean
+        self.out_best = self._to_numpy_out(mean)
+        if K >= 2:
+            self.posterior_std = self._to_numpy_out(torch.sqrt(self._post_m2 / float(K - 1)))
+        with torch.no_grad():
+            if self._holdout_dev is None:
+                _, metrics = ops.masked_loss(mean, self.img_, self.mask_, self.loss_kind)
+                self.posterior_snr = float(metrics[1].item())
+            else:
+                _, metrics = ops.masked_loss_holdout(mean, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
+                m = metrics[:10].tolist()
+                self.posterior_snr, self.posterior_val_snr = float(m[1]), float(m[9])
+
+    def _print_posterior(self):
+        if self.posterior_samples is None:
+            print("posterior: no iteration was sampled (%d run, burn-in %d): the output is the selected iterate"
+                  % (self.iiter, self.posterior_burnin))
+            return
+        msg = "posterior mean over %d samples: SNR %+.2f dB" % (self.posterior_samples, self.posterior_snr)
+        if self.posterior_val_snr is not None:
+            msg += ", held-out SNR %+.2f dB (selected iterate: %+.2f dB)" % (self.posterior_val_snr, self.holdout_snr())
+        print(msg)
 
     def training_mask(self):
         """The mask of the samples the network may see: mask_ itself without --holdout, else m_tr = mask_ * (1 - h) (drawn here if the patch
@@ -290,6 +383,8 @@ class Interpolator:
                                             _lib.ptr(input_), _lib.stream()), "dpi_axpy")
             self.input_list.append(u.torch_to_np(input_, True))
         out_ = self.net(input_)
+        if self.is_sampler():
+            self._moments_update(out_)
         if self._holdout_dev is None:
             total_loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, self.loss_kind)
         else:
@@ -410,7 +505,7 @@ class Interpolator:
             large = int(np.prod(self.img.shape[:-1])) >= (1 << 20)
             mode = "eager" if (net_inputs is not None or a.save_every is not None or a.epochs < 3 or self.has_regularizer()
                                or a.data_forgetting_factor != 0 or self.noise_source() != "philox" or big or (large and a.epochs < 1000)) else "graph"
-        self.optimizer = FusedAdam(self.net.parameters(), lr=a.lr)
+        self.optimizer = self.make_optimizer()
         ops.set_weight_grad_overlap(big, in_graph=(mode == "graph" and big))
         start = time()
         if mode == "graph" and self.noise_source() != "philox":
@@ -432,11 +527,14 @@ class Interpolator:
                     break
             torch.cuda.synchronize(self.device)
             self.out_best = self._to_numpy_out(self._out_best_dev)
+            self._finish_posterior()
         self.elapsed = time() - start
         if verbose:
             print("\n" + u.sec2time(self.elapsed))
             if self._holdout_dev is not None:
                 print("held-out SNR %+.2f dB at iteration %d (the selected output)" % (self.holdout_snr(), self.best_iter + 1))
+            if self.is_sampler():
+                self._print_posterior()
 
     def holdout_snr(self):
         """val_snr of the selected output (iteration best_iter) of the last optimised patch; None without --holdout."""
@@ -457,7 +555,7 @@ class Interpolator:
         L = _lib.load()
         dev = self.device
         if self.optimizer is None:
-            self.optimizer = FusedAdam(self.net.parameters(), lr=a.lr)
+            self.optimizer = self.make_optimizer()
             # prepared directly (optimize_concurrently, bench.py): the weight-gradient side streams follow THIS patch's size, not
             # whatever an earlier optimize() in the process left behind; optimize() / bench.py set it before they
             # call graph_prepare with an optimiser of their own
@@ -482,6 +580,8 @@ class Interpolator:
             ops.begin_iteration()
             opt.zero_grad()
             out_ = self.net(self.perturbed_input())
+            if self.is_sampler():
+                self._moments_update(out_)
             if ho is None:
                 loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, kind)
             else:
@@ -537,6 +637,7 @@ class Interpolator:
         self.iiter = n
         self._out_best_dev = self._g_best
         self.out_best = self._to_numpy_out(self._g_best)
+        self._finish_posterior()
 
     def _optimize_graph(self, verbose, check_every):
         graph = self.graph_prepare()
@@ -577,6 +678,9 @@ class Interpolator:
             # flat patch that was not optimised
             run["holdout"] = None if self.holdout_sel is None else self.holdout_sel[None]
             run["best_iter"] = self.best_iter
+        if self.is_sampler():
+            run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
+                       posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)
         np.save(os.path.join(self.outpath, self.image_name + "_run.npy"), run)
         if self.args.savemodel:
             torch.save(self.net.state_dict(), os.path.join(self.outpath, self.image_name + "_model.pth"))
@@ -586,6 +690,8 @@ class Interpolator:
         self.loss_min = None
         self.best_iter = self.val_min = None
         self._out_best_dev = None
+        self._reset_posterior()
+        self._zero_moments()
         self.history = self._new_history()
 
     def _new_history(self):

@@ -28,6 +28,9 @@ class Interpolator(_Base):
         if getattr(args, "holdout", 0.0) > 0.0:
             raise ValueError("main_pocs does not support --holdout (got %g): the POCS projection re-inserts every known trace into its "
                              "target, held-out ones included; run main.py for self-validation" % args.holdout)
+        if getattr(args, "optimizer", "adam") != "adam":
+            raise ValueError("main_pocs does not support --optimizer %s: the POCS target follows the current output, there is no fixed "
+                             "posterior to sample; run main.py for Langevin sampling" % args.optimizer)
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

@@ -93,6 +93,20 @@ _FLAGS = [
     (("--holdout",), dict(type=float, required=False, default=0.0,
                           help="Fraction in [0, 0.5] of the known traces withheld from the loss (0 = off).  The output with the lowest misfit on "
                                "them is kept and early stopping follows that misfit; each trace is drawn independently from the patch seed")),
+    # Langevin sampling (ours: the reference ships architectures/optimizers.py — SGLD, pSGLD — without a caller, main.py:200 builds Adam)
+    (("--optimizer",), dict(type=str, required=False, default="adam", choices=["adam", "sgld", "psgld"],
+                           help="ours: adam (reference), or a Langevin sampler of the reference's optimizers.py: the output becomes the mean of "
+                                "the iterates after --posterior_burnin and their spread is saved as posterior_std")),
+    (("--weight_decay",), dict(type=float, required=False, default=0.0, help="ours: L2 penalty of the Langevin samplers (sgld, psgld)")),
+    (("--sgld_noise_scale",), dict(type=float, required=False, default=0.1, help="ours: variance of the isotropic noise of sgld (SGLD noise_scale)")),
+    (("--psgld_beta",), dict(type=float, required=False, default=0.99, help="ours: decay of the squared-gradient average of psgld (pSGLD beta)")),
+    (("--psgld_lambda",), dict(type=float, required=False, default=1e-8, help="ours: added to the preconditioner of psgld (pSGLD Lambda)")),
+    (("--langevin_temperature",), dict(type=float, required=False,
+                                      help="ours: factor on the VARIANCE of the injected noise.  Unset = 1/N with N the number of samples the "
+                                           "loss averages over (non-zeros of the patch's training mask): our loss is a mean, not a sum, so the "
+                                           "reference's noise rule over-heats it N-fold; 1 = the reference's rule verbatim; 0 = no noise")),
+    (("--posterior_burnin",), dict(type=int, required=False, help="ours: iterations before the first sampled one (default: half of --epochs)")),
+    (("--posterior_thin",), dict(type=int, required=False, help="ours: sample every K-th iteration after the burn-in (default 1)")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -125,7 +139,38 @@ def postprocess(args: Namespace) -> Namespace:
         args.netdir = []
     if not 0.0 <= getattr(args, "holdout", 0.0) <= 0.5:
         raise ValueError("--holdout must lie in [0, 0.5], got %r" % args.holdout)
+    _postprocess_sampler(args)
     return args
+
+
+def _postprocess_sampler(args: Namespace) -> None:
+    """Ranges and derived defaults of the Langevin flags (ours).  The sampler-only flags are refused with --optimizer adam, where they
+    would silently do nothing."""
+    opt = getattr(args, "optimizer", "adam")
+    if opt not in ("adam", "sgld", "psgld"):
+        raise ValueError("--optimizer must be adam, sgld or psgld, got %r" % (opt,))
+    sampler_only = ("langevin_temperature", "posterior_burnin", "posterior_thin")
+    if opt == "adam":
+        given = [k for k in sampler_only if getattr(args, k, None) is not None]
+        if given:
+            raise ValueError("--%s needs a sampler (--optimizer sgld or psgld), not --optimizer adam" % ", --".join(given))
+        args.posterior_burnin, args.posterior_thin = args.epochs // 2, 1        # the listed defaults; inert without a sampler
+        return
+    for k in ("weight_decay", "sgld_noise_scale", "psgld_beta", "psgld_lambda"):
+        if not getattr(args, k) >= 0.0:
+            raise ValueError("--%s must be >= 0, got %r" % (k, getattr(args, k)))
+    if args.psgld_beta > 1.0:
+        raise ValueError("--psgld_beta must lie in [0, 1], got %r" % args.psgld_beta)
+    if args.langevin_temperature is not None and not args.langevin_temperature >= 0.0:
+        raise ValueError("--langevin_temperature must be >= 0, got %r" % args.langevin_temperature)
+    if args.posterior_burnin is None:
+        args.posterior_burnin = args.epochs // 2
+    if args.posterior_burnin < 0:
+        raise ValueError("--posterior_burnin must be >= 0, got %r" % args.posterior_burnin)
+    if args.posterior_thin is None:
+        args.posterior_thin = 1
+    if args.posterior_thin < 1:
+        raise ValueError("--posterior_thin must be >= 1, got %r" % args.posterior_thin)
 
 
 def parse_arguments(argv=None) -> Namespace:

@@ -344,6 +344,27 @@ typedef struct { float* p; const float* g; float* m; float* v; } dpi_adam_tensor
 int dpi_adam_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors,
                    const float* step_lr, double beta1, double beta2, double eps, const int* active,
                    void* stream);
+/* Langevin samplers in one launch for all tensors.  Replaces architectures/optimizers.py:79-106 (SGLD.step, momentum 0) and :144-181
+ * (pSGLD.step, not centred), which the reference ships without a caller.  Table, sizes, step_lr {step already incremented, lr}, `active`
+ * and the grid are those of dpi_adam_multi; the `m` slot is unused, pSGLD keeps V in the `v` slot.  With d = g + weight_decay * p (only
+ * when weight_decay != 0):
+ *   kind 0 (SGLD):   p -= lr * d;  p += sqrt(noise_scale) * sqrt(temperature) * xi
+ *   kind 1 (pSGLD):  V = beta * V + (1 - beta) * d * d;  G = sqrt(V) + lambda;  p -= lr * d / G;  p += sqrt(2 * lr / G) * sqrt(temperature) * xi
+ * in the operation order and with the rounding points of the torch CPU calls the reference makes (csrc/loss_optim.hip); sqrt(temperature)
+ * is a separate fp32 factor, so temperature 1 is the reference's rule.  xi (device array of `ntensors` device pointers, row order of the
+ * table) holds the standard normals; xi == NULL draws them in the kernel: Philox4x32-10 with key `seed`, stream id
+ * (0xFFFFFFFE << 32) | step (read from step_lr[0] on the device: a replayed graph draws fresh noise) and counter (row << 40) | q, q the
+ * group of four consecutive elements of the tensor — the normals dpi_fill_normal(mean 0, std 1) writes for that stream on row 0. */
+int dpi_langevin_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors, const float* step_lr, int kind,
+                       double weight_decay, double beta, double lambda, double noise_scale, double temperature, uint64_t seed,
+                       const float* const* xi, const int* active, void* stream);
+/* Posterior moments of the network output over the sampled iterations (the iterate averaging of the Bayesian deep-image-prior use of
+ * optimizers.py; the reference has no caller).  it = (int)step_lr[0]: called BEFORE the optimiser step of an iteration it is the 0-based
+ * iteration index.  Nothing happens when *active == 0 (active may be NULL), it < burn_in or (it - burn_in) % thin != 0; otherwise, with
+ * k = (it - burn_in) / thin + 1 (Welford):  delta = out - mean;  mean += delta / k;  m2 += delta * (out - mean).
+ * out, mean, m2: device float[n]. */
+int dpi_moments_update(const float* out, float* mean, float* m2, size_t n, const float* step_lr, int burn_in, int thin,
+                       const int* active, void* stream);
 
 /* ---------------------------------------------------------------- device-resident loop control --
  * Replaces the host-side bookkeeping of main.py:165-182,214-217 so that a captured hipGraph of one iteration can be
