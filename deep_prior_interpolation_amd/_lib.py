@@ -111,6 +111,11 @@ SIGNATURES = {
     "dpi_pocs_project": (_I, [_P, _P, _P, _Z, _P, _P]),
     "dpi_overlap_add": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "dpi_overlap_normalize": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
+    # weighted re-assembly (--reassembly cover / --blend taper / the std volume): (mean, std, pd, ph, pw, od, oh, ow, ramp_d, ld, ramp_h, lh,
+    # ramp_w, lw, sides, acc, K, D, H, W, stream) and (acc, K, D, H, W, gain, out_mean, out_std, stream).  ABI_VERSION stays: a stale library
+    # fails on the unresolved symbols
+    "dpi_overlap_add_weighted": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _U, _P, _I, _I, _I, _I, _P]),
+    "dpi_overlap_finalize_weighted": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P]),
     # ABI 400: the same calls with the storage types of their activation / gradient tensors (`io` before the stream)
     "dpi_channel_stats_io": (_I, [_P, _P, _I, _Z, _P, _U, _P]),
     "dpi_chain_apply_io": (_I, [_P, _P, _I, _Z, _P, _U, _P]),

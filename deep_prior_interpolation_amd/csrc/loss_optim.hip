@@ -337,6 +337,93 @@ __global__ __launch_bounds__(256) void overlap_norm_kernel(float* __restrict__ a
   }
 }
 
+// ---- weighted overlap-add (--reassembly cover / --blend taper / the std volume of a sampler run) ------------------------------------
+// Axis weight of sample i of a p-sample window: ramp[i] over the first l samples where the low side tapers, ramp[p-1-i] over the last l
+// where the high side does, 1 elsewhere (l <= p/2: the two never meet).
+struct BlendAxis {
+  const float* ramp;
+  int l, lo, hi;
+};
+__device__ __forceinline__ float blend_weight(const BlendAxis& a, int i, int p) {
+  if (a.lo && i < a.l) return a.ramp[i];
+  if (a.hi && i >= p - a.l) return a.ramp[p - 1 - i];
+  return 1.f;
+}
+
+// One pass over the patch, a thread per four consecutive samples of a row (W is the contiguous axis): plane 0 += w, plane 1 += w * mean,
+// plane 2 += w * std^2 (K = 3).  16-byte accesses where rows, origin and every base allow them (wave-uniform), else the same four
+// samples one by one.  Every accumulator element is read and written by one thread: plain stores, launches of one stream serialise.
+__global__ __launch_bounds__(256) void overlap_add_weighted_kernel(const float* __restrict__ mean, const float* __restrict__ sd, int pd, int ph,
+                                                                   int pw, int od, int oh, int ow, BlendAxis ad, BlendAxis ah, BlendAxis aw,
+                                                                   float* __restrict__ acc, int D, int H, int W) {
+  const int qpr = (pw + 3) >> 2;                               // quads per row
+  const size_t nq = (size_t)pd * ph * qpr, plane = (size_t)D * H * W;
+  const bool vec = (pw & 3) == 0 && (ow & 3) == 0 && (W & 3) == 0 && dpi_vec4_base(mean, false) && dpi_vec4_base(acc, false) &&
+                   (!sd || dpi_vec4_base(sd, false));
+  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < nq; t += (size_t)gridDim.x * 256) {
+    const int q = (int)(t % qpr);
+    const size_t row = t / qpr;
+    const int h = (int)(row % ph), d = (int)(row / ph), w0 = q * 4;
+    const float wdh = blend_weight(ad, d, pd) * blend_weight(ah, h, ph);
+    const size_t src = row * pw + w0;
+    const size_t dst = ((size_t)(od + d) * H + (oh + h)) * W + ow + w0;
+    if (vec) {
+      const float4 m = dpi_ld4(mean, src, false, false);
+      const float4 wt = make_float4(wdh * blend_weight(aw, w0, pw), wdh * blend_weight(aw, w0 + 1, pw), wdh * blend_weight(aw, w0 + 2, pw),
+                                    wdh * blend_weight(aw, w0 + 3, pw));
+      float4 a0 = dpi_ld4(acc, dst, false, false), a1 = dpi_ld4(acc, plane + dst, false, false);
+      a0.x += wt.x; a0.y += wt.y; a0.z += wt.z; a0.w += wt.w;
+      a1.x += wt.x * m.x; a1.y += wt.y * m.y; a1.z += wt.z * m.z; a1.w += wt.w * m.w;
+      dpi_st4(acc, dst, a0, false, false);
+      dpi_st4(acc, plane + dst, a1, false, false);
+      if (sd) {
+        const float4 s = dpi_ld4(sd, src, false, false);
+        float4 a2 = dpi_ld4(acc, 2 * plane + dst, false, false);
+        a2.x += wt.x * (s.x * s.x); a2.y += wt.y * (s.y * s.y); a2.z += wt.z * (s.z * s.z); a2.w += wt.w * (s.w * s.w);
+        dpi_st4(acc, 2 * plane + dst, a2, false, false);
+      }
+    } else {
+      for (int k = 0; k < 4 && w0 + k < pw; ++k) {
+        const float wt = wdh * blend_weight(aw, w0 + k, pw);
+        acc[dst + k] += wt;
+        acc[plane + dst + k] += wt * mean[src + k];
+        if (sd) { const float s = sd[src + k]; acc[2 * plane + dst + k] += wt * (s * s); }
+      }
+    }
+  }
+}
+
+// mean = plane 1 / plane 0 / gain, std = sqrt(plane 2 / plane 0) / |gain|; a sample no window reached (weight 0) gives 0.
+__device__ __forceinline__ void blend_finalize_element(float w, float a1, float a2, float gain, float& m, float& s) {
+  m = w > 0.f ? a1 / w / gain : 0.f;
+  s = w > 0.f ? sqrtf(a2 / w) / fabsf(gain) : 0.f;
+}
+__global__ __launch_bounds__(256) void overlap_finalize_weighted_kernel(const float* __restrict__ acc, int K, size_t n, float gain,
+                                                                        float* __restrict__ out_mean, float* __restrict__ out_std) {
+  const bool vec = (n & 3) == 0 && dpi_vec4_base(acc, false) && dpi_vec4_base(out_mean, false) && (!out_std || dpi_vec4_base(out_std, false));
+  const bool sq = K == 3 && out_std;
+  if (vec) {
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 1024) {
+      const float4 w = dpi_ld4(acc, i, false, false), a1 = dpi_ld4(acc, n + i, false, false);
+      const float4 a2 = sq ? dpi_ld4(acc, 2 * n + i, false, false) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 m, s;
+      blend_finalize_element(w.x, a1.x, a2.x, gain, m.x, s.x);
+      blend_finalize_element(w.y, a1.y, a2.y, gain, m.y, s.y);
+      blend_finalize_element(w.z, a1.z, a2.z, gain, m.z, s.z);
+      blend_finalize_element(w.w, a1.w, a2.w, gain, m.w, s.w);
+      dpi_st4(out_mean, i, m, false, false);
+      if (sq) dpi_st4(out_std, i, s, false, false);
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+      float m, s;
+      blend_finalize_element(acc[i], acc[n + i], sq ? acc[2 * n + i] : 0.f, gain, m, s);
+      out_mean[i] = m;
+      if (sq) out_std[i] = s;
+    }
+  }
+}
+
 // ---- device-resident loop control (one thread): history row, best-output flag, ReduceLROnPlateau, EarlyStopping ---------
 // state (double[8]): {iter, loss_min, plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved}
 __global__ void loop_control_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist,
@@ -526,6 +613,37 @@ extern "C" int dpi_overlap_normalize(float* acc, int D, int H, int W, int pd, in
   DPI_REQUIRE(acc && pd <= D && ph <= H && pw <= W && sd > 0 && sh > 0 && sw > 0 && gain != 0.f, "overlap_normalize: bad argument");
   overlap_norm_kernel<<<nblocks((size_t)D * H * W), 256, 0, (hipStream_t)stream>>>(acc, D, H, W, pd, ph, pw, sd, sh, sw, gain);
   return dpi_check_launch("overlap_normalize");
+}
+
+extern "C" int dpi_overlap_add_weighted(const float* mean, const float* std, int pd, int ph, int pw, int od, int oh, int ow,
+                                        const float* ramp_d, int ld, const float* ramp_h, int lh, const float* ramp_w, int lw, unsigned sides,
+                                        float* acc, int K, int D, int H, int W, void* stream) {
+  DPI_REQUIRE(mean && acc && pd > 0 && ph > 0 && pw > 0, "overlap_add_weighted: bad argument");
+  DPI_REQUIRE(od >= 0 && oh >= 0 && ow >= 0 && od <= D - pd && oh <= H - ph && ow <= W - pw,
+              "overlap_add_weighted: patch (%d,%d,%d)@(%d,%d,%d) outside volume (%d,%d,%d)", pd, ph, pw, od, oh, ow, D, H, W);
+  DPI_REQUIRE(K == (std ? 3 : 2), "overlap_add_weighted: K = %d planes %s a std patch (2 = weight, mean; 3 = weight, mean, variance with one)", K,
+              std ? "with" : "without");
+  DPI_REQUIRE(ld >= 0 && lh >= 0 && lw >= 0 && ld <= pd / 2 && lh <= ph / 2 && lw <= pw / 2,
+              "overlap_add_weighted: ramp lengths (%d,%d,%d) must lie in [0, half the patch (%d,%d,%d)]", ld, lh, lw, pd, ph, pw);
+  DPI_REQUIRE((sides & ~63u) == 0, "overlap_add_weighted: sides = %u has bits beyond the six faces", sides);
+  DPI_REQUIRE((ld == 0 || ramp_d) && (lh == 0 || ramp_h) && (lw == 0 || ramp_w), "overlap_add_weighted: a ramp of non-zero length needs its table");
+  const BlendAxis ad = {ramp_d, ld, ld > 0 && (sides & 1u), ld > 0 && (sides & 2u)};
+  const BlendAxis ah = {ramp_h, lh, lh > 0 && (sides & 4u), lh > 0 && (sides & 8u)};
+  const BlendAxis aw = {ramp_w, lw, lw > 0 && (sides & 16u), lw > 0 && (sides & 32u)};
+  overlap_add_weighted_kernel<<<nblocks((size_t)pd * ph * cdivz(pw, 4)), 256, 0, (hipStream_t)stream>>>(mean, std, pd, ph, pw, od, oh, ow, ad, ah, aw,
+                                                                                                      acc, D, H, W);
+  return dpi_check_launch("overlap_add_weighted");
+}
+
+extern "C" int dpi_overlap_finalize_weighted(const float* acc, int K, int D, int H, int W, float gain, float* out_mean, float* out_std,
+                                             void* stream) {
+  DPI_REQUIRE(acc && out_mean && D > 0 && H > 0 && W > 0, "overlap_finalize_weighted: bad argument");
+  DPI_REQUIRE(K == 2 || K == 3, "overlap_finalize_weighted: K = %d planes (2 = weight, mean; 3 = weight, mean, variance)", K);
+  DPI_REQUIRE(!out_std || K == 3, "overlap_finalize_weighted: a std volume needs the variance plane (K = 3), got K = %d", K);
+  DPI_REQUIRE(gain != 0.f && gain == gain, "overlap_finalize_weighted: gain must be a non-zero number");
+  const size_t n = (size_t)D * H * W;
+  overlap_finalize_weighted_kernel<<<nblocks(cdivz(n, 4)), 256, 0, (hipStream_t)stream>>>(acc, K, n, gain, out_mean, out_std);
+  return dpi_check_launch("overlap_finalize_weighted");
 }
 
 extern "C" int dpi_loop_control(const double* metrics, double* state, double* hist, int max_iters, float* step_lr, int* active,

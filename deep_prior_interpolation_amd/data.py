@@ -2,7 +2,10 @@
 2.5-D slab transposes, and overlap-add reassembly from the per-patch result files.
 
 `reconstruct_patches` sorts the result files by patch name (the reference relies on directory order of an
-unsorted glob, data.py:99 — SURVEY App. B.7) and can run the overlap-add on the GPU (`device=`)."""
+unsorted glob, data.py:99 — SURVEY App. B.7).
+
+Ours, opt-in: --reassembly cover cuts (and re-assembles) one more, edge-flush window on every axis the regular grid leaves a tail on, --blend
+taper weights the overlaps (utils/patch_extractor.py); `reconstruct_patches(field="posterior_std")` blends the per-patch spread of a sampler run."""
 import os
 from glob import glob
 from typing import List
@@ -25,6 +28,15 @@ def patch_extractor_for(in_shape, patch_shape, patch_stride, datadim, imgchannel
 
 
 _get_patch_extractor = patch_extractor_for   # reference name
+
+
+def reassembly_flags(args):
+    """(cover, blend) of a Namespace; args.txt files of older runs and of the reference lack the keys: crop, flat."""
+    reassembly, blend = getattr(args, "reassembly", None) or "crop", getattr(args, "blend", None) or "flat"
+    if reassembly not in ("crop", "cover") or blend not in ("flat", "taper"):
+        raise ValueError("--reassembly must be crop or cover and --blend flat or taper, got %r, %r" % (reassembly, blend))
+    return reassembly == "cover", blend
+
 
 _TO_SLAB = {"xy": (0, 2, 3, 1), "ty": (0, 1, 3, 2)}   # B,T,X,Y -> B,X,Y,T  /  B,T,Y,X
 _FROM_SLAB = {"xy": (0, 3, 1, 2), "ty": (0, 1, 3, 2)}
@@ -53,8 +65,13 @@ def extract_patches(args) -> List[dict]:
         final_shape = (-1,) + pe.dim              # last axis = channels
     else:
         final_shape = (-1,) + pe.dim + (1,)
-    img = pe.extract(original).reshape(final_shape)
-    msk = pe.extract(corrupted).reshape(final_shape)
+    if reassembly_flags(args)[0]:
+        origins = u.window_origins(original.shape, pe.dim, pe.stride, cover=True)
+        img = u.extract_at(original, origins, pe.dim).reshape(final_shape)
+        msk = u.extract_at(corrupted, origins, pe.dim).reshape(final_shape)
+    else:
+        img = pe.extract(original).reshape(final_shape)
+        msk = pe.extract(corrupted).reshape(final_shape)
     if args.datadim == "2.5d":
         img = transpose_patches_25d(img, args.slice)
         msk = transpose_patches_25d(msk, args.slice)
@@ -68,8 +85,15 @@ def extract_patches(args) -> List[dict]:
     return out
 
 
-def reconstruct_patches(args, return_history=False, verbose=False, results_root="./results"):
-    """Re-assemble the volume from ./results/<outdir>/<name>_run.npy (data.py:87-130)."""
+def reconstruct_patches(args, return_history=False, verbose=False, results_root="./results", field="output"):
+    """Re-assemble the volume from ./results/<outdir>/<name>_run.npy (data.py:87-130).
+
+    field = "posterior_std" (a sampler run, --optimizer sgld | psgld) blends the per-patch spread instead:
+    sqrt(sum(w sigma^2) / sum(w)) / |gain|, a patch without one (skipped, or fewer than two samples) counting as 0.  --reassembly cover
+    returns the input's shape, --blend taper weights the overlaps; with the defaults and field = "output" nothing differs from before."""
+    if field not in ("output", "posterior_std"):
+        raise ValueError("field must be output or posterior_std, got %r" % (field,))
+    cover, blend = reassembly_flags(args)
     inputs = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     pe = patch_extractor_for(inputs.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
     pe.extract(inputs)
@@ -80,7 +104,8 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     outs, elapsed, history, dev = [], [], [], "?"
     for path in files:
         rec = np.load(path, allow_pickle=True).item()
-        outs.append(np.asarray(rec["output"]))
+        v = rec["output"] if field == "output" else rec.get(field)
+        outs.append(np.asarray(v) if v is not None else np.zeros_like(np.asarray(rec["output"])))
         elapsed.append(rec.get("elapsed", rec.get("elapsed time")))
         history.append(rec["history"])
         dev = rec.get("device", dev)
@@ -89,7 +114,12 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     patches_out = np.asarray(outs)
     if args.datadim == "2.5d":
         patches_out = transpose_patches_25d(patches_out, args.slice, adj=True)
-    outputs = pe.reconstruct(patches_out.reshape(pa_shape)) / args.gain
+    if not cover and blend == "flat" and field == "output":
+        outputs = pe.reconstruct(patches_out.reshape(pa_shape)) / args.gain
+    else:
+        origins = u.window_origins(inputs.shape, pe.dim, pe.stride, cover=cover)
+        outputs = u.reassemble(patches_out.reshape((-1,) + pe.dim), origins, u.reassembled_shape(inputs.shape, pe.dim, pe.stride, cover),
+                               pe.dim, pe.stride, blend, spread=field != "output") / (args.gain if field == "output" else abs(args.gain))
     if verbose:
         print("\n%d patches; total elapsed time on %s: %s"
               % (len(history), dev, u.sec2time(sum(u.time2sec(e) for e in elapsed if e))))

@@ -115,6 +115,7 @@ class Interpolator:
 
     def _reset_posterior(self):
         self.posterior_std = self.output_selected = self.posterior_samples = self.posterior_snr = self.posterior_val_snr = None
+        self._post_std_dev = None                                # posterior_std on the device, for the re-assembled std volume
 
     def _zero_moments(self):
         if self._post_mean is not None:
@@ -172,7 +173,8 @@ class Interpolator:
         self._out_best_dev = mean
         self.out_best = self._to_numpy_out(mean)
         if K >= 2:
-            self.posterior_std = self._to_numpy_out(torch.sqrt(self._post_m2 / float(K - 1)))
+            self._post_std_dev = torch.sqrt(self._post_m2 / float(K - 1))
+            self.posterior_std = self._to_numpy_out(self._post_std_dev)
         with torch.no_grad():
             if self._holdout_dev is None:
                 _, metrics = ops.masked_loss(mean, self.img_, self.mask_, self.loss_kind)

@@ -11,6 +11,8 @@ The only exchange is the
 final reassembly (reference data.reconstruct_patches, data.py:87-130): every rank overlap-adds its best outputs
 into a local full-volume accumulator and ONE all-reduce(sum) of that fp32 volume (RCCL over xGMI; gloo in the
 CPU tests) followed by the analytic hit-count normalisation gives every rank the reconstructed volume.
+With --reassembly cover, --blend taper or a sampler (--optimizer sgld | psgld) the accumulator is the weighted one instead
+(DeviceBlendAccumulator: stacked planes sum(w), sum(w mean) and, for a sampler, sum(w std^2); still ONE all-reduce, over the stack).
 
 One process per GPU: launch with `python -m torch.distributed.run --nproc-per-node N -m deep_prior_interpolation_amd.parallel ...`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment).
@@ -24,8 +26,8 @@ import torch.distributed as dist
 from . import _lib
 from . import utils as u
 
-__all__ = ["shard_indices", "PatchQueue", "DeviceOverlapAccumulator", "HostOverlapAccumulator", "gather_volume", "run_patches",
-           "optimise_volume", "main"]
+__all__ = ["shard_indices", "PatchQueue", "DeviceOverlapAccumulator", "HostOverlapAccumulator", "DeviceBlendAccumulator",
+           "HostBlendAccumulator", "gather_volume", "run_patches", "optimise_volume", "main"]
 
 
 def shard_indices(num_patches, rank, world):
@@ -117,6 +119,105 @@ class DeviceOverlapAccumulator:
         return self.acc.cpu().numpy()
 
 
+class HostBlendAccumulator:
+    """Weighted sibling of HostOverlapAccumulator (float64; utils.reassemble's arithmetic, patch by patch): stacked planes sum(w), sum(w p)
+    and, with_std, sum(w std^2) in ONE tensor, so gather_volume stays one all-reduce.  finalize() returns the mean; the blended spread is
+    left in `std_volume` (None without with_std)."""
+
+    def __init__(self, shape, dim, stride, device="cpu", taper=False, with_std=False):
+        self.shape, self.dim, self.stride = tuple(int(v) for v in shape), tuple(int(v) for v in dim), tuple(int(v) for v in stride)
+        self.taper, self.with_std = bool(taper), bool(with_std)
+        self.acc = torch.zeros((3 if with_std else 2,) + self.shape, dtype=torch.float64)
+        self.std_volume = None
+
+    def add(self, patch, origin, std=None):
+        sl = tuple(slice(int(o), int(o) + d) for o, d in zip(origin, self.dim))
+        w = torch.from_numpy(u.patch_window(self.shape, self.dim, self.stride, origin, self.taper))
+        self.acc[0][sl] += w
+        self.acc[1][sl] += w * torch.as_tensor(np.asarray(patch), dtype=torch.float64)
+        if self.with_std and std is not None:
+            self.acc[2][sl] += w * torch.as_tensor(np.asarray(std), dtype=torch.float64) ** 2
+
+    def tensor(self):
+        return self.acc
+
+    def finalize(self, gain):
+        den = self.acc[0]
+        safe = torch.where(den > 0, den, torch.ones_like(den))
+        if self.with_std:
+            self.std_volume = (torch.where(den > 0, torch.sqrt(self.acc[2] / safe), torch.zeros_like(den)) / abs(gain)).numpy()
+        return (torch.where(den > 0, self.acc[1] / safe, torch.zeros_like(den)) / gain).numpy()
+
+
+class DeviceBlendAccumulator:
+    """fp32 stacked accumulator [K][D][H][W] in HBM for the weighted re-assembly (dpi_overlap_add_weighted / dpi_overlap_finalize_weighted):
+    plane 0 = sum(w), 1 = sum(w mean), 2 = sum(w std^2) with_std.  The ramp tables are uploaded here, once; add() copies nothing from the
+    host but a patch that is not on the device yet.  finalize() returns the mean volume and leaves the std volume in `std_volume`."""
+
+    def __init__(self, shape, dim, stride, device, taper=False, with_std=False):
+        if len(shape) != 3:
+            raise NotImplementedError("device overlap-add handles 3-D volumes; use HostBlendAccumulator otherwise")
+        self.shape, self.dim, self.stride = tuple(int(s) for s in shape), tuple(int(d) for d in dim), tuple(int(s) for s in stride)
+        self.taper, self.with_std = bool(taper), bool(with_std)
+        self.K = 3 if self.with_std else 2
+        self.acc = torch.zeros((self.K,) + self.shape, dtype=torch.float32, device=device)
+        self.ramps = [torch.from_numpy(u.taper_ramp(d, s).astype(np.float32)).to(device) if taper and u.taper_length(d, s) > 0 else None
+                      for d, s in zip(self.dim, self.stride)]
+        self._zero_std = None
+        self.std_volume = None
+
+    def _patch(self, patch, what):
+        p = patch if torch.is_tensor(patch) else torch.from_numpy(np.ascontiguousarray(patch, dtype=np.float32))
+        p = p.to(self.acc.device, torch.float32).contiguous()
+        if tuple(p.shape) != self.dim:
+            raise _lib.DpiError("overlap_add_weighted: %s shape %s != %s" % (what, tuple(p.shape), self.dim))
+        return p
+
+    def add(self, patch, origin, std=None):
+        """std=None with_std: the patch has no spread (skipped, or fewer than two samples) and contributes std 0."""
+        p = self._patch(patch, "patch")
+        sd = None
+        if self.with_std:
+            if std is None:
+                if self._zero_std is None:
+                    self._zero_std = torch.zeros(self.dim, dtype=torch.float32, device=self.acc.device)
+                sd = self._zero_std
+            else:
+                sd = self._patch(std, "std")
+        elif std is not None:
+            raise _lib.DpiError("overlap_add_weighted: a std patch needs an accumulator built with_std")
+        origin = [int(o) for o in origin]
+        sides, ramp_args = 0, []
+        for k, (n, d, o, r) in enumerate(zip(self.shape, self.dim, origin, self.ramps)):
+            lo, hi = u.taper_sides(n, d, o)
+            sides |= (int(lo) << (2 * k)) | (int(hi) << (2 * k + 1))
+            ramp_args += [_lib.ptr(r), 0 if r is None else r.numel()]
+        _lib.check(_lib.load().dpi_overlap_add_weighted(_lib.ptr(p), _lib.ptr(sd), *self.dim, *origin, *ramp_args, sides, _lib.ptr(self.acc),
+                                                        self.K, *self.shape, _lib.stream()), "dpi_overlap_add_weighted")
+
+    def tensor(self):
+        return self.acc
+
+    def finalize(self, gain):
+        mean = torch.empty(self.shape, dtype=torch.float32, device=self.acc.device)
+        std = torch.empty_like(mean) if self.with_std else None
+        _lib.check(_lib.load().dpi_overlap_finalize_weighted(_lib.ptr(self.acc), self.K, *self.shape, float(gain), _lib.ptr(mean), _lib.ptr(std),
+                                                             _lib.stream()), "dpi_overlap_finalize_weighted")
+        self.std_volume = None if std is None else std.cpu().numpy()
+        return mean.cpu().numpy()
+
+
+def _acc_add(acc, T, origin):
+    """Overlap-add the output T selected for its patch; a weighted accumulator of a sampler run takes the patch's posterior std with it."""
+    if getattr(acc, "with_std", False):
+        sd = getattr(T, "_post_std_dev", None)
+        if sd is not None and sd.is_cuda:
+            sd.record_stream(torch.cuda.current_stream(sd.device))      # made on the patch's stream, read here, dropped by T.clean() right after
+        acc.add(T._best_for_acc, origin, std=None if sd is None else sd.reshape(sd.shape[2:]))
+    else:
+        acc.add(T._best_for_acc, origin)
+
+
 def gather_volume(acc):
     """The single data-path collective: all-reduce(sum) of the accumulator volume (no-op for world size 1)."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -125,13 +226,16 @@ def gather_volume(acc):
 
 
 def run_patches(patches, origins, vol_shape, dim, stride, gain, optimise_fn, rank=0, world=1, accumulator_cls=None,
-                device="cpu", queue=None):
+                device="cpu", queue=None, reassembly="crop", blend="flat"):
     """Optimise this rank's share with `optimise_fn(index, patch) -> best output (patch-shaped)`, overlap-add locally,
     all-reduce once, normalise.  `queue` (PatchQueue) hands out the indices; None = static round-robin shard.
-    Returns (reconstructed volume of the cropped shape, indices this rank processed)."""
-    accumulator_cls = accumulator_cls or HostOverlapAccumulator
-    cropped = u.in_content_cropped_shape(vol_shape, dim, stride)
-    acc = accumulator_cls(cropped, dim, stride, device)
+    reassembly="cover" (with the covering `origins`) or blend="taper" take the weighted accumulator (HostBlendAccumulator by default).
+    Returns (reconstructed volume: the cropped shape, the volume's own under cover; indices this rank processed)."""
+    out_shape = u.reassembled_shape(vol_shape, dim, stride, reassembly == "cover")
+    if reassembly != "crop" or blend != "flat":
+        acc = (accumulator_cls or HostBlendAccumulator)(out_shape, dim, stride, device, taper=blend == "taper")
+    else:
+        acc = (accumulator_cls or HostOverlapAccumulator)(out_shape, dim, stride, device)
     queue = queue or PatchQueue(len(patches), static=(rank, world))
     mine = []
     while True:
@@ -226,7 +330,7 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
     rep = _Replayer(device, int(os.environ.get("DPI_SLOT_DEPTH", "6")))
 
     def done(T, i):
-        acc.add(T._best_for_acc, origins[i])
+        _acc_add(acc, T, origins[i])
         if save:
             T.save_result()
         _record_holdout(T, holdout_snrs)
@@ -333,18 +437,28 @@ def _print_holdout_summary(rank, holdout_snrs):
 
 
 def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None, conc=1, queue=None, save=True, timings=None,
-                    holdout_snrs=None):
+                    holdout_snrs=None, volumes=None):
     """Deep-prior optimisation of every patch this rank pulls from `queue`, `conc` patches at a time on one GPU, overlap-added
     into a device accumulator; ONE all-reduce at the end; returns (reconstructed volume, indices processed here).
 
     conc > 1 (DPI_CONCURRENT_PATCHES): every patch of a group gets its own Interpolator, stream and captured iteration graph
     (main.optimize_concurrently).  Patches whose loop cannot run as a graph (--save_every, data forgetting, >= 2^20 voxels)
     and flat patches are handled one by one.  save=False skips the per-patch result files (bench.py).  holdout_snrs (list, --holdout):
-    the held-out SNR of every optimised patch's selected output is appended to it."""
+    the held-out SNR of every optimised patch's selected output is appended to it.
+
+    --reassembly cover (with the covering `patches` / `origins`: the result has `vol_shape`), --blend taper and a sampler
+    (--optimizer sgld | psgld) switch to DeviceBlendAccumulator; a sampler run blends the per-patch posterior std too and leaves that
+    volume in volumes["std"] (volumes: a dict of the caller's).  With none of them the accumulator and its kernels are the ones of before."""
     from time import perf_counter
+    from .data import reassembly_flags
     from .main import Interpolator, optimize_concurrently
-    cropped = u.in_content_cropped_shape(vol_shape, pe.dim, pe.stride)
-    acc = DeviceOverlapAccumulator(cropped, pe.dim, pe.stride, device)
+    cover, blend = reassembly_flags(args)
+    sampler = getattr(args, "optimizer", "adam") != "adam"
+    if cover or blend != "flat" or sampler:
+        acc = DeviceBlendAccumulator(u.reassembled_shape(vol_shape, pe.dim, pe.stride, cover), pe.dim, pe.stride, device,
+                                     taper=blend == "taper", with_std=sampler)
+    else:
+        acc = DeviceOverlapAccumulator(u.in_content_cropped_shape(vol_shape, pe.dim, pe.stride), pe.dim, pe.stride, device)
     if args.start_from_prev:
         if conc > 1:
             raise _lib.DpiError("--start_from_prev chains the patches of a process one after the other (reference main.py:286): "
@@ -399,7 +513,7 @@ def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None,
         for T in live:
             T._best_for_acc = T._out_best_dev.reshape(T._out_best_dev.shape[2:])
         for T, i in zip(Ts, group):
-            acc.add(T._best_for_acc, origins[i])
+            _acc_add(acc, T, origins[i])
             if save:
                 T.save_result()
             _record_holdout(T, holdout_snrs)
@@ -417,13 +531,15 @@ def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None,
     else:
         gather_volume(acc)
     rec = acc.finalize(args.gain)
+    if volumes is not None:
+        volumes["std"] = getattr(acc, "std_volume", None)
     return rec, mine
 
 
 def main(argv=None):
     """Multi-GPU counterpart of main.main(): same flags; each rank optimises the patches it pulls from the shared queue, result
     files are written per patch exactly as in the single-process run, rank 0 additionally saves `reconstructed.npy`."""
-    from .data import extract_patches, patch_extractor_for
+    from .data import extract_patches, patch_extractor_for, reassembly_flags
     from .main import Interpolator
     from .parameter import parse_arguments
     args = parse_arguments(argv)
@@ -446,14 +562,17 @@ def main(argv=None):
     patches = extract_patches(args)
     vol = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     pe = patch_extractor_for(vol.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
-    origins = u.window_origins(vol.shape, pe.dim, pe.stride)
+    origins = u.window_origins(vol.shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
     conc = int(os.environ.get("DPI_CONCURRENT_PATCHES", "1"))
     queue = PatchQueue.for_process_group(len(patches), static=bool(args.start_from_prev))
     holdout_snrs = []
+    volumes = {}
+    sampler = getattr(args, "optimizer", "adam") != "adam"
     if args.datadim == "3d" and vol.ndim == 3:
         if (args.imgchannel or 1) != 1:
             raise _lib.DpiError("the device overlap-add path re-assembles single-channel 3-D volumes (imgchannel = 1)")
-        rec, mine = optimise_volume(args, patches, origins, vol.shape, pe, device, outpath, conc, queue, holdout_snrs=holdout_snrs)
+        rec, mine = optimise_volume(args, patches, origins, vol.shape, pe, device, outpath, conc, queue, holdout_snrs=holdout_snrs,
+                                    volumes=volumes)
     else:
         # 2-D / 2.5-D slabs: result files only; rank 0 re-assembles them on the host like the reference does
         from .data import reconstruct_patches
@@ -481,9 +600,14 @@ def main(argv=None):
         if world > 1:
             dist.barrier()
         rec = reconstruct_patches(args) if rank == 0 else None
+        if rank == 0 and sampler:
+            volumes["std"] = reconstruct_patches(args, field="posterior_std")
     _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
+        if sampler and volumes.get("std") is not None:
+            # the window-weighted mean of the per-patch posterior variances, as a std: the spread WITHIN the windows
+            np.save(os.path.join(outpath, "reconstructed_std.npy"), volumes["std"])
         print("rank 0: %d patches total, %d local; reconstructed volume %s saved" % (len(patches), len(mine), rec.shape))
     if world > 1:
         dist.destroy_process_group()

@@ -107,6 +107,13 @@ _FLAGS = [
                                            "reference's noise rule over-heats it N-fold; 1 = the reference's rule verbatim; 0 = no noise")),
     (("--posterior_burnin",), dict(type=int, required=False, help="ours: iterations before the first sampled one (default: half of --epochs)")),
     (("--posterior_thin",), dict(type=int, required=False, help="ours: sample every K-th iteration after the burn-in (default 1)")),
+    # re-assembly of the volume (ours: the reference crops to the regular window grid and averages overlaps with a box window)
+    (("--reassembly",), dict(type=str, required=False, default="crop", choices=["crop", "cover"],
+                            help="ours: crop = the regular window grid, which drops the tail of an axis where (n - d) %% s != 0 (reference); "
+                                 "cover = one more window flush with the end of such an axis: the result has the input's shape")),
+    (("--blend",), dict(type=str, required=False, default="flat", choices=["flat", "taper"],
+                       help="ours: flat = overlapping patches are averaged (reference); taper = weighted by sin^2 ramps over the overlap, "
+                            "which removes the step at every window edge")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),

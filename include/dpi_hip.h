@@ -417,6 +417,22 @@ int dpi_overlap_add(const float* patch, int pd, int ph, int pw, int od, int oh, 
                     int D, int H, int W, void* stream);
 int dpi_overlap_normalize(float* acc, int D, int H, int W, int pd, int ph, int pw, int sd, int sh,
                           int sw, float gain, void* stream);
+/* Weighted overlap-add (ours: --reassembly cover, --blend taper, the std volume of a sampler run; utils/patch_extractor.py `reassemble`
+ * defines the arithmetic).  acc is ONE stacked buffer [K][D][H][W], zeroed by the caller: plane 0 += w, plane 1 += w * mean, plane 2 +=
+ * w * std^2; K = 3 exactly when std (a patch of per-sample standard deviations, same shape as mean) is given, else 2.
+ * w = (w_d * w_h) * w_w in fp32; along an axis of p samples with a ramp table of l <= p/2 floats on the device (may be null when l = 0) the
+ * weight of sample i is ramp[i] for i < l where the low face tapers, ramp[p-1-i] for i >= p - l where the high face does, 1 elsewhere.
+ * sides: bit 0 / 1 = low / high face of the D axis, bits 2 / 3 of H, bits 4 / 5 of W; a face on the volume's edge is left out by the caller.
+ * One pass, a thread per four consecutive samples along W; 16-byte accesses when pw, ow and W are multiples of 4 and mean, std and acc sit
+ * on 16 bytes, one sample at a time otherwise.  No atomics: calls that add into one acc go to one stream (or are ordered by events). */
+int dpi_overlap_add_weighted(const float* mean, const float* std /*nullable*/, int pd, int ph, int pw, int od, int oh, int ow,
+                             const float* ramp_d, int ld, const float* ramp_h, int lh, const float* ramp_w, int lw, unsigned sides,
+                             float* acc, int K, int D, int H, int W, void* stream);
+/* out_mean = plane 1 / plane 0 / gain; out_std (nullable; needs K = 3) = sqrt(plane 2 / plane 0) / |gain|: the window-weighted mean of the
+ * per-patch variances, i.e. the spread WITHIN the windows, not the disagreement between overlapping patches.  A sample of weight 0 gives 0.
+ * out_mean and out_std are [D][H][W] buffers of their own (not planes of acc). */
+int dpi_overlap_finalize_weighted(const float* acc, int K, int D, int H, int W, float gain, float* out_mean, float* out_std /*nullable*/,
+                                  void* stream);
 
 /* ---------------------------------------------------------------- anti-aliasing operators -------
  * Linear operators of the anti-aliasing add-on (BASELINE configs[3]); `adjoint` != 0 applies the exact transpose, which is
