@@ -95,6 +95,11 @@ SIGNATURES = {
     "dpi_copy_if": (_I, [_P, _P, _P, _Z, _P]),
     "dpi_masked_loss_holdout": (_I, [_P, _P, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P]),     # ABI 406: --holdout
     "dpi_loop_control_holdout": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, C.c_double, C.c_double, _I, C.c_double, _P]),
+    # --out_ema: (out, avg, img, mask, sel|NULL, C, T, S, kind, beta, step_lr, active|NULL, ws, result, stream) and
+    # (metrics, ema_metrics, has_holdout, state, hist, max_iters, step_lr, active, improved, use_plateau, factor, threshold, patience, min_lr,
+    # lr_eps, es_patience, es_min_delta, stream).  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_ema_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, _P]),
+    "dpi_loop_control_ema": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, C.c_double, C.c_double, _I, C.c_double, _P]),
     "dpi_noise_add": (_I, [_P, _Z, _F, _U64, _P, _P, _P]),
     "dpi_fill_normal": (_I, [_P, _Z, _F, _F, _U64, _U64, _P]),
     "dpi_fir_axis0": (_I, [_P, _P, _I, _I, _I, _Z, _P, _P]),

@@ -1,4 +1,4 @@
-// Masked L1/MSE loss with fused gradient and SNR/PCORR sums, multi-tensor Adam, Philox input noise,
+// Masked L1/MSE loss with fused gradient and SNR/PCORR sums, the running average of the output (--out_ema), multi-tensor Adam, Philox input noise,
 // overlap-add patch reassembly.
 #include "common.h"
 
@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const float* __restri
   }
 }
 
-__global__ __launch_bounds__(64) void loss_final_kernel(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
+// the body of loss_final_kernel (one wave of 64); dpi_ema_loss finalises with it too
+__device__ __forceinline__ void loss_final(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
   double acc[7];
 #pragma unroll
   for (int k = 0; k < 7; ++k) {
@@ -48,6 +49,9 @@ __global__ __launch_bounds__(64) void loss_final_kernel(const double* __restrict
     res[0] = loss; res[1] = snr; res[2] = cov / (sqrt(vt) * sqrt(vo));
     res[3] = acc[1]; res[4] = acc[2]; res[5] = acc[3]; res[6] = acc[4]; res[7] = acc[5];
   }
+}
+__global__ __launch_bounds__(64) void loss_final_kernel(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
+  loss_final(ws, nblk, n, res);
 }
 
 // ---- masked loss with held-out traces (--holdout) ------------------------------------------------------------------
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(256) void loss_holdout_partial_kernel(const float* 
   }
 }
 
-__global__ __launch_bounds__(64) void loss_holdout_final_kernel(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
+__device__ __forceinline__ void loss_holdout_final(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
   double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = threadIdx.x; b < nblk; b += 64) {          // per k the order of loss_final_kernel; the 12 loads of a row issue together
 #pragma unroll
@@ -112,6 +116,69 @@ __global__ __launch_bounds__(64) void loss_holdout_final_kernel(const double* __
     res[3] = acc[1]; res[4] = acc[2]; res[5] = acc[3]; res[6] = acc[4]; res[7] = acc[5];
     res[8] = acc[8] / acc[11]; res[9] = 10.0 * log10(acc[9] / acc[10]); res[10] = acc[11];
   }
+}
+__global__ __launch_bounds__(64) void loss_holdout_final_kernel(const double* __restrict__ ws, int nblk, double n, double* __restrict__ res) {
+  loss_holdout_final(ws, nblk, n, res);
+}
+
+// ---- running average of the net output (--out_ema) -------------------------------------------------------------
+// avg <- out at iteration 0 (whatever avg held: it is not read), else avg + w * (out - avg) with w = fp32(1 - beta); in the same pass the
+// sums of loss_partial_kernel (HO = false: grid, walk, partial layout and order of dpi_masked_loss) or of loss_holdout_partial_kernel
+// (HO = true) on the value just stored, so the finalisers below give the metrics of the stored average bit for bit as the loss pass would
+// on it.  No gradient: the deep-image-prior out_avg only selects and reports.  avg is read and written once, by one thread per element.
+template <bool HO>
+__global__ __launch_bounds__(256) void ema_loss_partial_kernel(const float* __restrict__ out, float* __restrict__ avg,
+                                                               const float* __restrict__ img, const float* __restrict__ mask,
+                                                               const float* __restrict__ sel, uint32_t TS, uint32_t S, size_t n, int kind,
+                                                               float w, const float* __restrict__ step_lr, const int* __restrict__ active,
+                                                               double* __restrict__ ws) {
+  if (active && *active == 0) return;
+  const bool first = (int)step_lr[0] == 0;
+  double acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const size_t G = (size_t)gridDim.x * 256;
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t Gc = 0, Gr = 0, Gs = 0, c = 0, r = 0, s = 0;
+  if (HO) {
+    Gc = (uint32_t)(G / TS); Gr = (uint32_t)(G % TS); Gs = (uint32_t)(G % S);
+    c = (uint32_t)(i / TS); r = (uint32_t)(i % TS); s = (uint32_t)(i % S);               // i = c * TS + r, s = i mod S (n < 2^32)
+  }
+  for (; i < n; i += G) {
+    const float x = out[i];
+    float o = x;
+    if (!first) { const float p = avg[i]; o = p + w * (x - p); }
+    avg[i] = o;
+    const float t = img[i], m0 = mask[i];
+    const float h = HO ? sel[(size_t)c * S + s] : 0.f;
+    const float m = HO ? m0 * (1.f - h) : m0;
+    const float d = o * m - t * m;
+    if (kind == 1) acc[0] += (double)d * d;
+    else acc[0] += fabsf(d);
+    const float e = t - o;
+    acc[1] += (double)t * t; acc[2] += (double)e * e; acc[3] += o; acc[4] += t;
+    acc[5] += (double)o * o; acc[6] += (double)o * t;
+    if (HO) {
+      const float mh = m0 * h;
+      const float eh = e * mh, th = t * mh;
+      acc[7] += kind == 1 ? (double)eh * eh : (double)fabsf(eh);
+      acc[8] += (double)th * th; acc[9] += (double)eh * eh; acc[10] += mh != 0.f ? 1.0 : 0.0;
+      c += Gc; r += Gr; s += Gs;
+      if (r >= TS) { r -= TS; ++c; }
+      if (s >= S) s -= S;
+    }
+  }
+  __shared__ double sh[4];
+#pragma unroll
+  for (int k = 0; k < (HO ? 11 : 7); ++k) {
+    const double v = block_sum(acc[k], sh);
+    if (threadIdx.x == 0) ws[(size_t)blockIdx.x * (HO ? 16 : 8) + (k < 7 ? k : k + 1)] = v;
+  }
+}
+
+__global__ __launch_bounds__(64) void ema_final_kernel(const double* __restrict__ ws, int nblk, double n, int ho, const int* __restrict__ active,
+                                                       double* __restrict__ res) {
+  if (active && *active == 0) return;                      // the partials are stale: result stays
+  if (ho) loss_holdout_final(ws, nblk, n, res);
+  else loss_final(ws, nblk, n, res);
 }
 
 // ---- Adam -----------------------------------------------------------------------------------------------------
@@ -499,6 +566,54 @@ __global__ void loop_control_holdout_kernel(const double* __restrict__ metrics, 
   state[0] = (double)(it + 1);
 }
 
+// The same with a running average of the output (--out_ema), with or without a held-out part: metrics = the raw iterate's doubles
+// (dpi_masked_loss[_holdout]), ema = those of the stored average (dpi_ema_loss).  History rows: the 4 (6 with a holdout) raw columns, then
+// {ema_loss, ema_snr[, ema_val_loss, ema_val_snr]}.  *improved, best_iter, early stopping and the NaN stop follow the average's selection
+// misfit q = ema_val_loss with a holdout, else ema_loss; ReduceLROnPlateau the raw training loss.
+// state (double[12]): {iter, loss_min (raw training), plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved,
+//                      val_min (raw held-out, holdout only), best_iter, q_min, reserved}
+__global__ void loop_control_ema_kernel(const double* __restrict__ metrics, const double* __restrict__ ema, int ho, double* __restrict__ state,
+                                        double* __restrict__ hist, int max_iters, float* __restrict__ step_lr, int* __restrict__ active,
+                                        int* __restrict__ improved, int use_plateau, double factor, double threshold, int patience,
+                                        double min_lr, double lr_eps, int es_patience, double es_min_delta) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  *improved = 0;
+  if (!*active) return;
+  const int it = (int)state[0];
+  const double loss = metrics[0];
+  const double q = ho ? ema[8] : ema[0];
+  const double lr = (double)step_lr[1];
+  if (it < max_iters) {
+    double* row = hist + (ho ? 10 : 6) * (size_t)it;
+    row[0] = loss; row[1] = metrics[1]; row[2] = metrics[2]; row[3] = lr;
+    if (ho) { row[4] = metrics[8]; row[5] = metrics[9]; row += 2; }
+    row[4] = ema[0]; row[5] = ema[1];
+    if (ho) { row[6] = ema[8]; row[7] = ema[9]; }
+  }
+  if (it == 0 || loss <= state[1]) state[1] = loss;
+  if (ho && (it == 0 || metrics[8] <= state[8])) state[8] = metrics[8];
+  if (it == 0 || q <= state[10]) { state[10] = q; state[9] = (double)it; *improved = 1; }
+  if (use_plateau) {
+    if (loss < state[2] * (1.0 - threshold)) { state[2] = loss; state[3] = 0.0; }
+    else state[3] += 1.0;
+    if (state[3] > (double)patience) {
+      const double nl = fmax(lr * factor, min_lr);
+      if (lr - nl > lr_eps) step_lr[1] = (float)nl;
+      state[3] = 0.0;
+    }
+  }
+  if (es_patience != 0) {
+    if (state[6] == 0.0) { state[4] = q; state[6] = 1.0; }
+    else if (q != q) *active = 0;
+    else {
+      if (q < state[4] - state[4] * es_min_delta / 100.0) { state[5] = 0.0; state[4] = q; }
+      else state[5] += 1.0;
+      if (state[5] >= (double)es_patience) *active = 0;
+    }
+  }
+  state[0] = (double)(it + 1);
+}
+
 __global__ __launch_bounds__(256) void copy_if_kernel(const int* __restrict__ flag, const float* __restrict__ src, float* __restrict__ dst,
                                                       size_t n) {
   if (*flag == 0) return;
@@ -544,6 +659,29 @@ extern "C" int dpi_masked_loss_holdout(const float* out, const float* img, const
   if (int e = dpi_check_launch("loss_holdout_partial")) return e;
   loss_holdout_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>(ws, (int)nb, (double)n, result);
   return dpi_check_launch("loss_holdout_final");
+}
+
+extern "C" int dpi_ema_loss(const float* out, float* avg, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
+                            int kind, float beta, const float* step_lr, const int* active, double* ws, double* result, void* stream) {
+  DPI_REQUIRE(out && avg && img && mask && step_lr && ws && result && C > 0 && T > 0 && S > 0, "ema_loss: bad argument");
+  DPI_REQUIRE(kind == 0 || kind == 1, "ema_loss: kind must be 0 (L1) or 1 (MSE)");
+  DPI_REQUIRE(beta >= 0.f && beta < 1.f, "ema_loss: beta = %g must lie in [0, 1)", (double)beta);
+  const size_t n = (size_t)C * T * S;
+  // the trace index is 32-bit (dpi_masked_loss_holdout)
+  DPI_REQUIRE(!sel || n <= (size_t)0xFFFFFFFFu - (size_t)kLossBlocks * 256, "ema_loss: %zu samples: the trace index is 32-bit", n);
+  size_t nb = cdivz(n, 256 * 8);                           // the grid of dpi_masked_loss
+  if (nb > kLossBlocks) nb = kLossBlocks;
+  if (nb < 1) nb = 1;
+  const float w = (float)(1.0 - (double)beta);
+  if (sel)
+    ema_loss_partial_kernel<true><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(out, avg, img, mask, sel, (uint32_t)((size_t)T * S), (uint32_t)S, n,
+                                                                               kind, w, step_lr, active, ws);
+  else
+    ema_loss_partial_kernel<false><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(out, avg, img, mask, nullptr, 0u, 0u, n, kind, w, step_lr, active,
+                                                                                ws);
+  if (int e = dpi_check_launch("ema_loss_partial")) return e;
+  ema_final_kernel<<<1, 64, 0, (hipStream_t)stream>>>(ws, (int)nb, (double)n, sel != nullptr, active, result);
+  return dpi_check_launch("ema_final");
 }
 
 extern "C" int dpi_adam_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors, const float* step_lr,
@@ -662,6 +800,17 @@ extern "C" int dpi_loop_control_holdout(const double* metrics, double* state, do
   loop_control_holdout_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, use_plateau,
                                                                 factor, threshold, patience, min_lr, lr_eps, es_patience, es_min_delta);
   return dpi_check_launch("loop_control_holdout");
+}
+
+extern "C" int dpi_loop_control_ema(const double* metrics, const double* ema_metrics, int has_holdout, double* state, double* hist,
+                                    int max_iters, float* step_lr, int* active, int* improved, int use_plateau, double factor,
+                                    double threshold, int patience, double min_lr, double lr_eps, int es_patience, double es_min_delta,
+                                    void* stream) {
+  DPI_REQUIRE(metrics && ema_metrics && state && hist && step_lr && active && improved && max_iters > 0, "loop_control_ema: bad argument");
+  loop_control_ema_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, ema_metrics, has_holdout != 0, state, hist, max_iters, step_lr, active,
+                                                            improved, use_plateau, factor, threshold, patience, min_lr, lr_eps, es_patience,
+                                                            es_min_delta);
+  return dpi_check_launch("loop_control_ema");
 }
 
 extern "C" int dpi_copy_if(const int* flag, const float* src, float* dst, size_t n, void* stream) {

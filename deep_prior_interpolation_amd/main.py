@@ -16,7 +16,7 @@ from . import utils as u
 from .architectures import get_net
 from .data import extract_patches
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import net_args_are_same, parse_arguments
+from .parameter import check_out_ema, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -41,6 +41,10 @@ class Interpolator:
             raise ValueError("--holdout must lie in [0, 0.5], got %r" % self.holdout)
         self.holdout_sel = self._holdout_dev = None              # per-trace selection: numpy (patch order without t) / device (C, S...)
         self.best_iter = self.val_min = None
+        # --out_ema (ours): the output is selected from an exponential running average of the iterates (deep image prior's out_avg)
+        self.out_ema = check_out_ema(args)
+        self._ema_avg = self._ema_best = self._ema_one = None    # per patch: the average, its selected snapshot, a constant 1 flag
+        self.ema_min = None
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
         self.optimizer_kind = getattr(args, "optimizer", "adam")
         if self.optimizer_kind not in ("adam", "sgld", "psgld"):
@@ -156,6 +160,45 @@ class Interpolator:
         _lib.check(_lib.load().dpi_moments_update(_lib.ptr(o), _lib.ptr(self._post_mean), _lib.ptr(self._post_m2), o.numel(),
                                                   _lib.ptr(opt.step_lr), self.posterior_burnin, self.posterior_thin, _lib.ptr(opt.active),
                                                   _lib.stream()), "dpi_moments_update")
+
+    # ---- running average of the output (--out_ema) -------------------------------------------------------------
+    def _ema_pass(self, out_):
+        """Fold the output of this iteration into the running average (reset on the device at iteration 0 of the optimiser's step counter:
+        call before optimizer.step()) and return the device metrics of the stored average.  The buffers live as long as the patch (clean())."""
+        o = out_.detach()
+        if self._ema_avg is None or self._ema_avg.shape != o.shape:
+            self._ema_avg = torch.empty(o.shape, dtype=torch.float32, device=o.device)
+            self._ema_best = torch.empty_like(self._ema_avg)
+            self._ema_one = torch.ones(1, dtype=torch.int32, device=o.device)
+        opt = self.optimizer
+        return ops.ema_loss(o, self._ema_avg, self.img_, self.mask_, self._holdout_dev, self.out_ema, opt.step_lr, opt.active, self.loss_kind)
+
+    def _select_ema(self, em):
+        """The eager loop's half of dpi_loop_control_ema, on the doubles of the same read-back: out_best follows the selection misfit of the
+        AVERAGE (ema_val_loss with --holdout, else ema_loss); the selected average is snapshot on the device (dpi_copy_if with a constant 1
+        flag: the next iteration overwrites the average itself)."""
+        ho = self._holdout_dev is not None
+        self.history.append_ema(em[0], em[1], *((em[8], em[9]) if ho else ()))
+        q = em[8] if ho else em[0]
+        improved, self.ema_min, self.best_iter = u.select_latest_min(self.iiter, q, self.ema_min, self.best_iter)
+        if improved:
+            _lib.check(_lib.load().dpi_copy_if(_lib.ptr(self._ema_one), _lib.ptr(self._ema_avg), _lib.ptr(self._ema_best),
+                                               self._ema_avg.numel(), _lib.stream()), "dpi_copy_if")
+            self._out_best_dev = self._ema_best
+        self._last_val = q
+
+    def _read_back(self, metrics, ema):
+        """The one read-back of an iteration: the raw iterate's doubles and, with --out_ema, the average's."""
+        if ema is None:
+            return (metrics[:10] if self._holdout_dev is not None else metrics[:3]).tolist(), None
+        both = torch.cat([metrics, ema]).tolist()
+        return both[:metrics.numel()], both[metrics.numel():]
+
+    def ema_snr(self):
+        """ema_snr of the selected average (iteration best_iter) of the last optimised patch; None without --out_ema."""
+        if self.best_iter is None or not hasattr(self.history, "ema_snr"):
+            return None
+        return float(self.history.ema_snr[self.best_iter])
 
     def _finish_posterior(self):
         """After the loop of a sampler run (eager and graph): out_best becomes the posterior mean over the K sampled iterations, the
@@ -387,6 +430,7 @@ class Interpolator:
         out_ = self.net(input_)
         if self.is_sampler():
             self._moments_update(out_)
+        ema = self._ema_pass(out_) if self.out_ema > 0.0 else None
         if self._holdout_dev is None:
             total_loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, self.loss_kind)
         else:
@@ -395,7 +439,7 @@ class Interpolator:
         if reg is None:
             total_loss.backward()
             ops.finish_backward(self._grad_params())
-            m = metrics[:10].tolist() if self._holdout_dev is not None else metrics[:3].tolist()       # one read-back
+            m, em = self._read_back(metrics, ema)                  # one read-back
             l, s, p = m[:3]
             self.history.append((l, s, p))
         else:
@@ -403,12 +447,21 @@ class Interpolator:
             total = total_loss + eps * reg_loss
             total.backward()
             ops.finish_backward(self._grad_params())
-            m = metrics[:10].tolist() if self._holdout_dev is not None else metrics[:3].tolist()
+            m, em = self._read_back(metrics, ema)
             main_l, s, p = m[:3]
             l, r = float(total.item()), float(reg_loss.item())
             self.history.append((l, main_l, r, s, p))           # HistoryReg layout (main_pocs.py:198-202)
         self.history.lr.append(self.optimizer.param_groups[0]["lr"])
-        if self._holdout_dev is None:
+        if em is not None:
+            # --out_ema: the raw columns as ever, the selection from the average
+            if self.iiter == 0 or l <= self.loss_min:
+                self.loss_min = l
+            if self._holdout_dev is not None:
+                self.history.append_val(m[8], m[9])
+                if self.iiter == 0 or m[8] <= self.val_min:
+                    self.val_min = m[8]
+            self._select_ema(em)
+        elif self._holdout_dev is None:
             if self.iiter == 0 or l <= self.loss_min:
                 self.loss_min = l
                 self._out_best_dev = out_.detach()   # stays on the GPU; copied to the host once, after the loop
@@ -493,7 +546,9 @@ class Interpolator:
         the `active` flag every `check_every` replays.  Same arithmetic, same stopping iteration.
         "auto" picks "graph" unless per-iteration host work was requested (net_inputs, --save_every) or the patch has >= 2^20 voxels
         (eager with the weight-gradient and branch streams).
-        --holdout: out_best and early stopping follow the misfit on the held-out traces, ReduceLROnPlateau the training loss."""
+        --holdout: out_best and early stopping follow the misfit on the held-out traces, ReduceLROnPlateau the training loss.
+        --out_ema: out_best is the running average of the outputs at the iteration where ITS misfit (training, or held-out with --holdout)
+        was lowest, and early stopping follows that misfit; the gradient and ReduceLROnPlateau see the raw iterate as ever."""
         a = self.args
         self._ensure_holdout()
         big = self.wants_weight_grad_overlap()
@@ -525,7 +580,7 @@ class Interpolator:
                     sched.step(loss)
                 if verbose:
                     print(self.history.log_message(self.iiter - 1), "\r", end="")
-                if stopper.step(loss if self._holdout_dev is None else self._last_val):
+                if stopper.step(loss if (self._holdout_dev is None and self.out_ema == 0.0) else self._last_val):
                     break
             torch.cuda.synchronize(self.device)
             self.out_best = self._to_numpy_out(self._out_best_dev)
@@ -535,14 +590,18 @@ class Interpolator:
             print("\n" + u.sec2time(self.elapsed))
             if self._holdout_dev is not None:
                 print("held-out SNR %+.2f dB at iteration %d (the selected output)" % (self.holdout_snr(), self.best_iter + 1))
+            if self.out_ema > 0.0:
+                print("running average (beta %g) selected at iteration %d: SNR %+.2f dB" % (self.out_ema, self.best_iter + 1, self.ema_snr()))
             if self.is_sampler():
                 self._print_posterior()
 
     def holdout_snr(self):
-        """val_snr of the selected output (iteration best_iter) of the last optimised patch; None without --holdout."""
+        """val_snr of the selected output (iteration best_iter) of the last optimised patch — with --out_ema the selected average's,
+        ema_val_snr; None without --holdout."""
         if self.best_iter is None or not hasattr(self.history, "val_snr"):
             return None
-        return float(self.history.val_snr[self.best_iter])
+        col = self.history.ema_val_snr if hasattr(self.history, "ema_val_snr") else self.history.val_snr
+        return float(col[self.best_iter])
 
     # ---- hipGraph path -------------------------------------------------------------------------------------
     def graph_prepare(self, quiet_device=True):
@@ -566,8 +625,11 @@ class Interpolator:
         opt = self.optimizer
         self._ensure_holdout()
         ho = self._holdout_dev
-        cols = 4 if ho is None else 6                    # history row {loss, snr, pcorr, lr[, val_loss, val_snr]}
-        self._g_state = torch.zeros(8 if ho is None else 10, dtype=torch.float64, device=dev)
+        ema_on = self.out_ema > 0.0
+        # history row {loss, snr, pcorr, lr[, val_loss, val_snr][, ema_loss, ema_snr[, ema_val_loss, ema_val_snr]]}
+        cols = (4 if ho is None else 6) + ((2 if ho is None else 4) if ema_on else 0)
+        self._g_layout = (ho is not None, ema_on)
+        self._g_state = torch.zeros(12 if ema_on else (8 if ho is None else 10), dtype=torch.float64, device=dev)
         self._g_state[2] = float("inf")
         self._g_hist = torch.zeros(a.epochs * cols, dtype=torch.float64, device=dev)
         self._g_improved = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -584,6 +646,7 @@ class Interpolator:
             out_ = self.net(self.perturbed_input())
             if self.is_sampler():
                 self._moments_update(out_)
+            ema = self._ema_pass(out_) if ema_on else None
             if ho is None:
                 loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, kind)
             else:
@@ -593,12 +656,18 @@ class Interpolator:
             opt.step()                                   # skipped on the device once `active` is 0
             if self._g_best is None:
                 self._g_best = torch.empty_like(out_)
-            control = L.dpi_loop_control if ho is None else L.dpi_loop_control_holdout
-            _lib.check(control(_lib.ptr(metrics), _lib.ptr(self._g_state), _lib.ptr(self._g_hist), a.epochs,
-                               _lib.ptr(opt.step_lr), _lib.ptr(opt.active), _lib.ptr(self._g_improved),
-                               int(bool(a.reduce_lr)), float(a.lr_factor), float(a.lr_thresh), int(a.lr_patience), 0.0, 1e-8,
-                               int(a.earlystop_patience), float(a.earlystop_min_delta), _lib.stream()), "dpi_loop_control")
-            _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(out_), _lib.ptr(self._g_best), out_.numel(),
+            rules = (int(bool(a.reduce_lr)), float(a.lr_factor), float(a.lr_thresh), int(a.lr_patience), 0.0, 1e-8,
+                     int(a.earlystop_patience), float(a.earlystop_min_delta), _lib.stream())
+            if ema_on:
+                _lib.check(L.dpi_loop_control_ema(_lib.ptr(metrics), _lib.ptr(ema), int(ho is not None), _lib.ptr(self._g_state),
+                                                  _lib.ptr(self._g_hist), a.epochs, _lib.ptr(opt.step_lr), _lib.ptr(opt.active),
+                                                  _lib.ptr(self._g_improved), *rules), "dpi_loop_control_ema")
+            else:
+                control = L.dpi_loop_control if ho is None else L.dpi_loop_control_holdout
+                _lib.check(control(_lib.ptr(metrics), _lib.ptr(self._g_state), _lib.ptr(self._g_hist), a.epochs,
+                                   _lib.ptr(opt.step_lr), _lib.ptr(opt.active), _lib.ptr(self._g_improved), *rules), "dpi_loop_control")
+            best_src = self._ema_avg if ema_on else out_         # --out_ema: the selected AVERAGE is kept
+            _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(best_src), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
 
         one_iteration()                                  # iteration 0, eager (also warms every lazy cache)
@@ -633,9 +702,17 @@ class Interpolator:
         self.history = self._new_history()
         self.history.loss, self.history.snr, self.history.pcorr, self.history.lr = (h[:, i].tolist() for i in range(4))
         self.loss_min = float(self._g_state[1].item())
-        if cols == 6:
+        ho, ema_on = self._g_layout
+        k = 4
+        if ho:
             self.history.val_loss, self.history.val_snr = h[:, 4].tolist(), h[:, 5].tolist()
             self.val_min, self.best_iter = float(self._g_state[8].item()), int(self._g_state[9].item())
+            k = 6
+        if ema_on:
+            self.history.ema_loss, self.history.ema_snr = h[:, k].tolist(), h[:, k + 1].tolist()
+            if ho:
+                self.history.ema_val_loss, self.history.ema_val_snr = h[:, k + 2].tolist(), h[:, k + 3].tolist()
+            self.best_iter, self.ema_min = int(self._g_state[9].item()), float(self._g_state[10].item())
         self.iiter = n
         self._out_best_dev = self._g_best
         self.out_best = self._to_numpy_out(self._g_best)
@@ -653,8 +730,11 @@ class Interpolator:
                     cols = self._g_hist.numel() // self.args.epochs
                     row = self._g_hist[cols * (n - 1):cols * n].tolist()
                     msg = "Iter %d, Loss = %+.2e, SNR = %+2.2f dB, PCORR = %+.2f %%" % (n, row[0], row[1], row[2] * 100)
-                    if cols == 6:
+                    ho, ema_on = self._g_layout
+                    if ho:
                         msg += ", VAL = %.2e, VSNR = %+.2f dB" % (row[4], row[5])
+                    if ema_on:
+                        msg += ", ESNR = %+.2f dB" % row[7 if ho else 5]
                     print(msg, "\r", end="")
         self.graph_finish()
 
@@ -680,6 +760,9 @@ class Interpolator:
             # flat patch that was not optimised
             run["holdout"] = None if self.holdout_sel is None else self.holdout_sel[None]
             run["best_iter"] = self.best_iter
+        if self.out_ema > 0.0:
+            run["out_ema"] = self.out_ema                        # `output` is the selected running average, best_iter its iteration
+            run["best_iter"] = self.best_iter
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)
@@ -690,16 +773,15 @@ class Interpolator:
     def clean(self):
         self.iiter = 0
         self.loss_min = None
-        self.best_iter = self.val_min = None
+        self.best_iter = self.val_min = self.ema_min = None
         self._out_best_dev = None
+        self._ema_avg = self._ema_best = None                    # the running average belongs to the patch
         self._reset_posterior()
         self._zero_moments()
         self.history = self._new_history()
 
     def _new_history(self):
-        if self.holdout > 0.0:
-            return u.HistoryRegHoldout(self.args.epochs) if self.has_regularizer() else u.HistoryHoldout(self.args.epochs)
-        return u.HistoryReg(self.args.epochs) if self.has_regularizer() else u.History(self.args.epochs)
+        return u.history_class(self.has_regularizer(), self.holdout > 0.0, self.out_ema > 0.0)(self.args.epochs)
 
 
 def optimize_concurrently(Ts, check_every=64, prepare=None, timings=None):

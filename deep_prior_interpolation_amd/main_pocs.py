@@ -31,6 +31,9 @@ class Interpolator(_Base):
         if getattr(args, "optimizer", "adam") != "adam":
             raise ValueError("main_pocs does not support --optimizer %s: the POCS target follows the current output, there is no fixed "
                              "posterior to sample; run main.py for Langevin sampling" % args.optimizer)
+        if (getattr(args, "out_ema", 0.0) or 0.0) != 0.0:
+            raise ValueError("main_pocs does not support --out_ema (got %g): the POCS target follows the current output, an average of "
+                             "outputs has no target of its own to be measured against; run main.py" % args.out_ema)
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

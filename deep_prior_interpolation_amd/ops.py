@@ -1587,3 +1587,32 @@ def masked_loss(out, img, mask, kind="mae"):
 
 def masked_loss_holdout(out, img, mask, sel, kind="mae"):
     return MaskedLossHoldoutFn.apply(out, img, mask, sel, 1 if kind == "mse" else 0)
+
+
+def ema_loss(out, avg, img, mask, sel, beta, step_lr, active=None, kind="mae"):
+    """--out_ema: fold `out` into the running average `avg` in place (avg = out at iteration 0 = step_lr[0], else avg + (1 - beta) * (out - avg))
+    and return the metrics of the stored average against img: device double[11] in the layout of masked_loss_holdout (sel None: double[8], the
+    layout of masked_loss).  No gradient flows: the iterate's own loss pass stays as it is.  out / avg / img / mask: (1, C, T, S...) fp32;
+    sel: (C, S...) or None; step_lr / active: the optimiser's device scalars."""
+    with torch.no_grad():
+        out, img, mask = _req(out.detach(), "ema output"), _req(img, "ema target"), _req(mask, "ema mask")
+        if not avg.is_contiguous():
+            raise _lib.DpiError("ema_loss: the average is updated in place and must be contiguous")
+        avg = _req(avg, "ema average")
+        if not (out.shape == avg.shape == img.shape == mask.shape) or out.ndim < 4 or out.shape[0] != 1:
+            raise _lib.DpiError("ema_loss: shapes %s / %s / %s / %s: expected four times (1, C, T, S...)"
+                                % (tuple(out.shape), tuple(avg.shape), tuple(img.shape), tuple(mask.shape)))
+        if sel is not None:
+            sel = _req(sel, "holdout selection")
+            if tuple(sel.shape) != (out.shape[1],) + tuple(out.shape[3:]):
+                raise _lib.DpiError("ema_loss: selection %s for an output %s: expected (C, S...)" % (tuple(sel.shape), tuple(out.shape)))
+        if not 0.0 <= float(beta) < 1.0:
+            raise ValueError("ema_loss: beta must lie in [0, 1), got %r" % (beta,))
+        L = _lib.load()
+        C_, T_ = out.shape[1], out.shape[2]
+        S_ = out.numel() // (C_ * T_)
+        ws = torch.empty(2 * L.dpi_loss_ws_doubles(out.numel()), dtype=torch.float64, device=out.device)
+        res = torch.empty(8 if sel is None else 11, dtype=torch.float64, device=out.device)
+        check(L.dpi_ema_loss(ptr(out), ptr(avg), ptr(img), ptr(mask), ptr(sel), C_, T_, S_, 1 if kind == "mse" else 0, float(beta),
+                             ptr(step_lr), ptr(active), ptr(ws), ptr(res), stream()), "dpi_ema_loss")
+        return res

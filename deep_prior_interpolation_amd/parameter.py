@@ -93,6 +93,12 @@ _FLAGS = [
     (("--holdout",), dict(type=float, required=False, default=0.0,
                           help="Fraction in [0, 0.5] of the known traces withheld from the loss (0 = off).  The output with the lowest misfit on "
                                "them is kept and early stopping follows that misfit; each trace is drawn independently from the patch seed")),
+    # running average of the output (ours: the out_avg of the deep-image-prior method, which the reference dropped)
+    (("--out_ema",), dict(type=float, required=False, default=0.0,
+                          help="ours: decay BETA in [0, 1) of an exponential running average of the network output (0 = off; deep image prior "
+                               "uses 0.99).  The output is selected from the average (lowest training misfit, or held-out misfit with "
+                               "--holdout) and early stopping follows that misfit; the weights' trajectory does not change.  Not with "
+                               "--optimizer sgld | psgld, whose posterior mean is that path's average")),
     # Langevin sampling (ours: the reference ships architectures/optimizers.py — SGLD, pSGLD — without a caller, main.py:200 builds Adam)
     (("--optimizer",), dict(type=str, required=False, default="adam", choices=["adam", "sgld", "psgld"],
                            help="ours: adam (reference), or a Langevin sampler of the reference's optimizers.py: the output becomes the mean of "
@@ -147,7 +153,20 @@ def postprocess(args: Namespace) -> Namespace:
     if not 0.0 <= getattr(args, "holdout", 0.0) <= 0.5:
         raise ValueError("--holdout must lie in [0, 0.5], got %r" % args.holdout)
     _postprocess_sampler(args)
+    check_out_ema(args)
     return args
+
+
+def check_out_ema(args: Namespace) -> float:
+    """Range of --out_ema and what it cannot be combined with; returns the value (0.0 for a Namespace without the key, as those of
+    reference args.txt files)."""
+    beta = getattr(args, "out_ema", 0.0)
+    beta = 0.0 if beta is None else float(beta)
+    if not 0.0 <= beta < 1.0:
+        raise ValueError("--out_ema must lie in [0, 1), got %r" % (beta,))
+    if beta > 0.0 and getattr(args, "optimizer", "adam") != "adam":
+        raise ValueError("--out_ema does not combine with --optimizer %s: the posterior mean is that path's average" % args.optimizer)
+    return beta
 
 
 def _postprocess_sampler(args: Namespace) -> None:

@@ -7,7 +7,8 @@ import torch
 
 from .generic import ten_digit
 
-__all__ = ["snr", "pcorr", "History", "HistoryReg", "HistoryHoldout", "HistoryRegHoldout"]
+__all__ = ["snr", "pcorr", "History", "HistoryReg", "HistoryHoldout", "HistoryRegHoldout", "HistoryEma", "HistoryRegEma",
+           "HistoryHoldoutEma", "HistoryRegHoldoutEma", "history_class", "select_latest_min"]
 
 
 def _lib(output, target):
@@ -132,3 +133,92 @@ class HistoryRegHoldout(_HoldoutColumns, HistoryReg):
     def __init__(self, epochs):
         HistoryReg.__init__(self, epochs)
         self.val_loss, self.val_snr = [], []
+
+
+class _EmaColumns:
+    """ema_loss / ema_snr columns of a run with --out_ema: the misfit and the SNR of the running average of the network output (the
+    out_avg of the deep-image-prior method), which is what such a run selects its output from.  With --holdout the classes below also
+    carry ema_val_loss / ema_val_snr, the average's numbers on the held-out samples."""
+    _emsg = ", ESNR = %+.2f dB"
+
+    def _init_ema(self, holdout):
+        self.ema_loss, self.ema_snr = [], []
+        if holdout:
+            self.ema_val_loss, self.ema_val_snr = [], []
+
+    def append_ema(self, ema_loss, ema_snr, ema_val_loss=None, ema_val_snr=None):
+        self.ema_loss.append(ema_loss)
+        self.ema_snr.append(ema_snr)
+        if hasattr(self, "ema_val_loss"):
+            self.ema_val_loss.append(ema_val_loss)
+            self.ema_val_snr.append(ema_val_snr)
+
+    def log_message(self, idx):
+        msg = super().log_message(idx) + self._emsg % self.ema_snr[idx]
+        if hasattr(self, "ema_val_snr"):
+            msg += ", EVSNR = %+.2f dB" % self.ema_val_snr[idx]
+        return msg
+
+    def __len__(self):
+        n = super().__len__()
+        assert len(self.ema_loss) == len(self.ema_snr) == n
+        if hasattr(self, "ema_val_loss"):
+            assert len(self.ema_val_loss) == len(self.ema_val_snr) == n
+        return n
+
+    def __str__(self):
+        s = super().__str__() + "\nELOSS: %s\nESNR : %s" % (self.ema_loss, self.ema_snr)
+        if hasattr(self, "ema_val_loss"):
+            s += "\nEVAL : %s\nEVSNR: %s" % (self.ema_val_loss, self.ema_val_snr)
+        return s
+
+    __repr__ = __str__
+
+
+class HistoryEma(_EmaColumns, History):
+    """History of a run with --out_ema."""
+
+    def __init__(self, epochs):
+        History.__init__(self, epochs)
+        self._init_ema(False)
+
+
+class HistoryRegEma(_EmaColumns, HistoryReg):
+    """HistoryReg of a run with --out_ema and a regulariser (--aa_weight): ema_loss is the pure data misfit of the average."""
+
+    def __init__(self, epochs):
+        HistoryReg.__init__(self, epochs)
+        self._init_ema(False)
+
+
+class HistoryHoldoutEma(_EmaColumns, HistoryHoldout):
+    """History of a run with --holdout and --out_ema."""
+
+    def __init__(self, epochs):
+        HistoryHoldout.__init__(self, epochs)
+        self._init_ema(True)
+
+
+class HistoryRegHoldoutEma(_EmaColumns, HistoryRegHoldout):
+    """HistoryReg of a run with --holdout, --out_ema and a regulariser."""
+
+    def __init__(self, epochs):
+        HistoryRegHoldout.__init__(self, epochs)
+        self._init_ema(True)
+
+
+def history_class(reg=False, holdout=False, ema=False):
+    """The History class of a run: reg = a regulariser splits the loss, holdout = --holdout > 0, ema = --out_ema > 0."""
+    return {(False, False, False): History, (True, False, False): HistoryReg,
+            (False, True, False): HistoryHoldout, (True, True, False): HistoryRegHoldout,
+            (False, False, True): HistoryEma, (True, False, True): HistoryRegEma,
+            (False, True, True): HistoryHoldoutEma, (True, True, True): HistoryRegHoldoutEma}[(bool(reg), bool(holdout), bool(ema))]
+
+
+def select_latest_min(it, misfit, best, best_iter):
+    """The selection rule of the loop, one iteration of it: (improved, best, best_iter) after iteration `it` (0-based) showed `misfit`.
+    Iteration 0 always selects; later ones when misfit <= best, so the later iterate wins a tie and a NaN never selects (after a NaN at
+    iteration 0 nothing does).  The device rule of dpi_loop_control_ema, on the same doubles."""
+    if it == 0 or misfit <= best:
+        return True, misfit, it
+    return False, best, best_iter

@@ -333,6 +333,20 @@ int dpi_masked_loss(const float* out, const float* img, const float* mask, size_
 int dpi_masked_loss_holdout(const float* out, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
                             int kind, float grad_scale, float* dout, double* ws, double* result, void* stream);
 
+/* Running average of the network output (--out_ema; the out_avg of the deep-image-prior method, which the reference dropped) with the
+ * metrics of the average in the same pass.  Tensors as dpi_masked_loss_holdout ([C][T][S], n = C*T*S); sel may be NULL (no held-out part).
+ * it = (int)step_lr[0]: called BEFORE the optimiser step of an iteration it is the 0-based iteration index (dpi_moments_update).
+ *   *active == 0 (active may be NULL): avg and result stay untouched.
+ *   it == 0:  avg = out, whatever avg held (it is not read: NaNs of a fresh buffer do not leak);
+ *   else      avg = avg + w * (out - avg) in fp32, w = (float)(1.0 - (double)beta), beta in [0, 1).
+ * result has the layout and the meaning of dpi_masked_loss_holdout evaluated on the stored avg (double[11]: training part on
+ * mask * (1 - sel), held-out part in [8..10]); with sel == NULL only result[0..7] are written, as dpi_masked_loss(avg, img, mask) writes
+ * them.  Grid, walk and summation order are those of the loss pass (double partials, fixed order, no atomics), so the numbers are bit for
+ * bit what that pass gives on avg.  There is no gradient: the iterate's own dpi_masked_loss[_holdout] call stays as it is.
+ * ws: double[2 * dpi_loss_ws_doubles(n)].  Traffic: out, avg, img, mask read, avg written: 20 B per sample. */
+int dpi_ema_loss(const float* out, float* avg, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
+                 int kind, float beta, const float* step_lr, const int* active, double* ws, double* result, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ---------------------
  * Replaces torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8).step() (main.py:200,213) for a list of
  * tensors in ONE launch.  ptrs: device array of {p, g, m, v} pointers per tensor; sizes: element counts;
@@ -385,6 +399,19 @@ int dpi_loop_control_holdout(const double* metrics, double* state, double* hist,
                              int* active, int* improved, int use_plateau, double factor, double threshold,
                              int patience, double min_lr, double lr_eps, int es_patience, double es_min_delta,
                              void* stream);
+/* dpi_loop_control for a run with --out_ema, with (has_holdout != 0) or without held-out traces.  metrics = the doubles of the raw iterate
+ * (dpi_masked_loss: 8, dpi_masked_loss_holdout: 11), ema_metrics = those of the stored average (dpi_ema_loss).  hist rows: the 4 raw columns
+ * {loss, snr, pcorr, lr} (6 with a holdout: + {val_loss, val_snr}), then {ema_loss, ema_snr} and, with a holdout, {ema_val_loss, ema_val_snr}:
+ * 6 or 10 doubles per iteration.  *improved and best_iter follow the average's selection misfit q = ema_val_loss with a holdout, else
+ * ema_loss (q <= q_min: the later iterate wins a tie; a NaN never improves); EarlyStopping(percentage) / the NaN stop follow q too;
+ * ReduceLROnPlateau follows the raw training loss metrics[0].  The caller keeps the selected average with dpi_copy_if(improved, avg, best).
+ * state: double[12], zero-initialised except state[2] = +inf:
+ *   [0] iter   [1] loss_min (raw training)   [2] plateau_best   [3] plateau_bad   [4] es_best   [5] es_bad   [6] es_has_best   [7] reserved
+ *   [8] val_min (raw held-out misfit; holdout only)   [9] best_iter   [10] q_min   [11] reserved */
+int dpi_loop_control_ema(const double* metrics, const double* ema_metrics, int has_holdout, double* state, double* hist,
+                         int max_iters, float* step_lr, int* active, int* improved, int use_plateau, double factor,
+                         double threshold, int patience, double min_lr, double lr_eps, int es_patience, double es_min_delta,
+                         void* stream);
 int dpi_copy_if(const int* flag, const float* src, float* dst, size_t n, void* stream);
 
 /* ---------------------------------------------------------------- input perturbation ------------
