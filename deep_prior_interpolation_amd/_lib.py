@@ -80,6 +80,11 @@ SIGNATURES = {
     "dpi_upsample2x_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dpi_crop_copy": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dpi_crop_copy_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # the attention gate of --net attmultiunet, attention.py:107-113: (x, q, C, D, H, W, scale_d, s_out, y, stream), (C, D, H, W, scale_d) and
+    # (dy, x, s, C, D, H, W, scale_d, dx, dq, ws, stream).  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_attn_gate_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dpi_attn_gate_bwd_ws_floats": (_Z, [_I, _I, _I, _I, _I]),
+    "dpi_attn_gate_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dpi_maxpool2x2_fwd": (_I, [_P, _I, _I, _I, _P, _P]),
     "dpi_maxpool2x2_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "dpi_deconv4x4s2_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -8,12 +8,13 @@ from .base import *            # noqa: F401,F403
 from .mulresunet import *      # noqa: F401,F403
 from .skip import *            # noqa: F401,F403
 from .unet import *            # noqa: F401,F403
+from .attention import *       # noqa: F401,F403
 from .unet import UNet
+from .attention import AttMulResUnet2D, AttMulResUnet3D
 from .mulresunet import MulResUnet, MulResUnet3D
 from .skip import Skip, Skip3D
 
 _OUT_OF_SCOPE = {
-    "attmultiunet": "AttMulResUnet2D (attention.py) is outside the hot-path scope (SURVEY §2 row 4f)",
     "part": "PartialUNet.forward(x, mask) cannot be called by Interpolator (SURVEY §2 row 4g)",
 }
 
@@ -22,6 +23,15 @@ def get_net(args, outchannel=1):
     net_name = getattr(args, "net", "multiunet")
     if net_name in _OUT_OF_SCOPE:
         raise NotImplementedError("--net %s: %s" % (net_name, _OUT_OF_SCOPE[net_name]))
+    if net_name == "attmultiunet":
+        # upstream routes 2d and 2.5d to AttMulResUnet2D (architectures/__init__.py:23-33) and has no 3-D attention net; AttMulResUnet3D is ours
+        if args.datadim == "2d":
+            raise NotImplementedError("--datadim 2d --net attmultiunet is held back on purpose: AttMulResUnet2D exists (architectures/attention.py), but the "
+                                      "host suite pins the 2d route of this factory as refused (tests/test_host.py); --datadim 2.5d builds the same net")
+        cls = AttMulResUnet3D if args.datadim == "3d" else AttMulResUnet2D
+        return cls(num_input_channels=args.inputdepth, num_output_channels=outchannel, num_channels_down=args.filters,
+                   upsample_mode=args.upsample, need_bias=True, act_fun=args.activation, last_act_fun=args.last_activation,
+                   dropout=args.dropout)
     common = dict(num_input_channels=args.inputdepth, num_output_channels=outchannel, upsample_mode=args.upsample,
                   need_bias=True, act_fun=args.activation, last_act_fun=args.last_activation, dropout=args.dropout)
     if args.datadim in ("2d", "2.5d"):

@@ -163,6 +163,28 @@ __device__ __forceinline__ void dpi_st_bf16_row(float* base, size_t i, float v, 
 static inline bool dpi_io_in(const dpi_conv_desc* d, bool flip) { return (d->io & (flip ? DPI_IO_DY_BF16 : DPI_IO_X_BF16)) != 0; }
 static inline bool dpi_io_out(const dpi_conv_desc* d, bool flip) { return (d->io & (flip ? DPI_IO_DX_BF16 : DPI_IO_Y_BF16)) != 0; }
 
+// ---- x2 linear up-sampling: taps of one axis (elementwise.hip, attention_gate.hip) -------------------
+// align_corners=False, scale 2: src = (o + .5)/2 - .5 clamped at 0  ->  even o: (.25, .75) on (o/2-1, o/2);
+// odd o: (.75, .25) on (o/2, o/2+1); indices edge-clamped.
+__device__ __forceinline__ void lin_src(int o, int n, int& i0, int& i1, float& w0, float& w1) {
+  const int h = o >> 1;
+  if (o & 1) { i0 = h; i1 = min(h + 1, n - 1); w0 = .75f; w1 = .25f; }
+  else { i0 = max(h - 1, 0); i1 = h; w0 = (h == 0) ? 0.f : .25f; w1 = (h == 0) ? 1.f : .75f; }
+}
+// the adjoint: the four outputs that read input i of an axis of length n (no = output length, <= 2 n) and their weights
+//   o = 2i-1: .25   o = 2i: .75 (+.25 at i = 0)   o = 2i+1: .75 (+.25 at i = n-1)   o = 2i+2: .25      (0 outside / cropped)
+__device__ __forceinline__ void lin_bwd_taps(int i, int n, int no, int (&o)[4], float (&wt)[4]) {
+  o[0] = 2 * i - 1; o[1] = 2 * i; o[2] = 2 * i + 1; o[3] = 2 * i + 2;
+  wt[0] = i > 0 ? .25f : 0.f;
+  wt[1] = i == 0 ? 1.f : .75f;
+  wt[2] = i == n - 1 ? 1.f : .75f;
+  wt[3] = i < n - 1 ? .25f : 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (o[k] < 0 || o[k] >= no) { wt[k] = 0.f; o[k] = 0; }
+  }
+}
+
 // ---- wave / block reductions (wave = 64 lanes) ------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

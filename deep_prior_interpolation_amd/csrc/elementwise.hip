@@ -855,14 +855,7 @@ __global__ __launch_bounds__(64) void channel_sum_final_kernel(const double* __r
   if (threadIdx.x == 0) out[c] = (float)s;
 }
 
-// ---- x2 up-sampling ------------------------------------------------------------------------------------------
-// align_corners=False, scale 2: src = (o + .5)/2 - .5 clamped at 0  ->  even o: (.25, .75) on (o/2-1, o/2);
-// odd o: (.75, .25) on (o/2, o/2+1); indices edge-clamped.
-__device__ __forceinline__ void lin_src(int o, int n, int& i0, int& i1, float& w0, float& w1) {
-  const int h = o >> 1;
-  if (o & 1) { i0 = h; i1 = min(h + 1, n - 1); w0 = .75f; w1 = .25f; }
-  else { i0 = max(h - 1, 0); i1 = h; w0 = (h == 0) ? 0.f : .25f; w1 = (h == 0) ? 1.f : .75f; }
-}
+// ---- x2 up-sampling (lin_src / lin_bwd_taps: common.h) -------------------------------------------------------
 
 template <bool xb = false, bool yb = false>
 __global__ __launch_bounds__(256) void upsample_fwd_kernel(const float* __restrict__ x, const float* __restrict__ chain, int D, int H,
@@ -997,19 +990,7 @@ __global__ __launch_bounds__(256) void upsample_lin_fwd_cube_kernel(const float*
   }
 }
 
-// backward: one thread per INPUT voxel gathers its 4x4x4 (3-D) / 4x4 (2-D) output neighbourhood with per-axis weights
-//   o = 2i-1: .25   o = 2i: .75 (+.25 at i = 0)   o = 2i+1: .75 (+.25 at i = n-1)   o = 2i+2: .25      (0 outside / cropped)
-__device__ __forceinline__ void lin_bwd_taps(int i, int n, int no, int (&o)[4], float (&wt)[4]) {
-  o[0] = 2 * i - 1; o[1] = 2 * i; o[2] = 2 * i + 1; o[3] = 2 * i + 2;
-  wt[0] = i > 0 ? .25f : 0.f;
-  wt[1] = i == 0 ? 1.f : .75f;
-  wt[2] = i == n - 1 ? 1.f : .75f;
-  wt[3] = i < n - 1 ? .25f : 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (o[k] < 0 || o[k] >= no) { wt[k] = 0.f; o[k] = 0; }
-  }
-}
+// backward: one thread per INPUT voxel gathers its 4x4x4 (3-D) / 4x4 (2-D) output neighbourhood with the per-axis weights of lin_bwd_taps
 
 template <bool SCALE_D, bool gb = false>
 __global__ __launch_bounds__(256) void upsample_lin_bwd_gather_kernel(const float* __restrict__ dy, int D, int H, int W, int Do, int Ho,

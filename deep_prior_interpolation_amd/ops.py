@@ -1393,6 +1393,57 @@ class ConcatCropFn(torch.autograd.Function):
         return tuple(outs)
 
 
+class AttentionGateFn(torch.autograd.Function):
+    """One decoder join of the attention MultiRes-UNet as a single node (reference attention.py:107-113, 257-260):
+         cat[:, :C] = skip * Upsample(x2, linear)(sigmoid(q))            cat[:, C:] = Upsample(x2, mode)(g)
+    Both producers write straight into the concatenated tensor, as SkipJoinFn does for the plain net; the C-channel gate is never formed.
+    The backward hands the two channel slices of d(cat) (contiguous for N = 1) to the gate's backward and the up-sampling adjoint.
+    fp32 only: the attention nets keep fp32 storage under --precision bf16 (Interpolator.storage_bf16_ok)."""
+
+    @staticmethod
+    def forward(ctx, skip, q, g, linear):
+        skip, q = _req(skip, "gate skip input"), _req(q, "gate map")
+        C_, Do, Ho, Wo = _dims(skip)
+        Cq, D, H, W = _dims(q)
+        scale_d = int(skip.ndim == 5)
+        Cg = 0
+        if g is not None:                   # None: the gated skip tensor alone (GridAttentionBlock.forward of the reference)
+            g = _req(g, "gate coarse input")
+            Cg = _dims(g)[0]
+        if skip.ndim != q.ndim or Cq != 1 or (g is not None and (g.ndim != q.ndim or _dims(g)[1:] != (D, H, W))):
+            raise ValueError("attention_gate: skip %s, gate map %s%s: expected a one-channel map on the coarse tensor's grid"
+                             % (tuple(skip.shape), tuple(q.shape), "" if g is None else " and coarse tensor %s" % (tuple(g.shape),)))
+        if (Do, Ho, Wo) != ((2 * D if scale_d else D), 2 * H, 2 * W):
+            raise ValueError("attention_gate: the skip tensor %s is not exactly twice the coarse grid of %s (every spatial size must be even at "
+                             "every scale)" % (tuple(skip.shape), tuple(q.shape)))
+        L = _lib.load()
+        cat = torch.empty(_like_spatial(skip, C_ + Cg, Do, Ho, Wo), dtype=torch.float32, device=skip.device)
+        s = torch.empty_like(q)
+        check(L.dpi_attn_gate_fwd(ptr(skip), ptr(q), C_, D, H, W, scale_d, ptr(s), ptr(cat[:, :C_]), stream()), "dpi_attn_gate_fwd")
+        if g is not None:
+            check(L.dpi_upsample2x_fwd(ptr(g), None, Cg, D, H, W, Do, Ho, Wo, int(linear), ptr(cat[:, C_:]), stream()), "dpi_upsample2x_fwd")
+        ctx.save_for_backward(skip, s)
+        ctx.geo = (C_, Cg, D, H, W, Do, Ho, Wo, scale_d, int(linear), q.shape, None if g is None else g.shape)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        dcat = _req(dcat, "attention-gate grad")
+        skip, s = ctx.saved_tensors
+        C_, Cg, D, H, W, Do, Ho, Wo, scale_d, linear, q_shape, g_shape = ctx.geo
+        L = _lib.load()
+        dskip = torch.empty_like(skip)
+        dq = torch.empty(q_shape, dtype=torch.float32, device=dcat.device)
+        ws = torch.empty(L.dpi_attn_gate_bwd_ws_floats(C_, D, H, W, scale_d), dtype=torch.float32, device=dcat.device)
+        check(L.dpi_attn_gate_bwd(ptr(dcat[:, :C_]), ptr(skip), ptr(s), C_, D, H, W, scale_d, ptr(dskip), ptr(dq), ptr(ws), stream()),
+              "dpi_attn_gate_bwd")
+        dg = None
+        if g_shape is not None and ctx.needs_input_grad[2]:
+            dg = torch.empty(g_shape, dtype=torch.float32, device=dcat.device)
+            raw_upsample2x_bwd(dcat[:, C_:], Cg, D, H, W, Do, Ho, Wo, linear, dg)
+        return dskip, dq, dg, None
+
+
 class MaskedLossFn(torch.autograd.Function):
     """loss_fn(out*mask, img*mask) of main.py:161 with the SNR / PCORR sums of main.py:166-167 in the same pass.
     Returns (loss, metrics) with metrics = device double[8] {loss, snr_dB, pcorr, ...}."""
@@ -1579,6 +1630,14 @@ def upsample2x(x, mode="nearest", out_size=None):
 
 def concat_crop(xs):
     return ConcatCropFn.apply(*xs)
+
+
+def attention_gate(skip, q, g, mode="nearest"):
+    """cat[skip * Upsample(x2, linear)(sigmoid(q)), Upsample(x2, mode)(g)] as one node (AttentionGateFn).  skip: (1, C, [2D,] 2H, 2W);
+    q: (1, 1, [D,] H, W); g: (1, Cg, [D,] H, W), or None for the gated skip tensor alone.  The gate is always up-sampled linearly (attention.py:102); `mode` is the decoder's."""
+    if mode not in ("nearest", "bilinear", "trilinear", "linear"):
+        raise NotImplementedError("upsample mode %r" % mode)
+    return AttentionGateFn.apply(skip, q, g, mode != "nearest")
 
 
 def masked_loss(out, img, mask, kind="mae"):

@@ -301,6 +301,21 @@ int dpi_crop_copy(const float* x, int C, int D, int H, int W, int od, int oh, in
 int dpi_crop_copy_bwd(const float* dy, int C, int D, int H, int W, int od, int oh, int ow, int Do,
                       int Ho, int Wo, float* dx, void* stream);
 
+/* ---------------------------------------------------------------- attention gate ----------------
+ * Replaces the tail of GridAttentionBlock.forward, `psi = Upsample(2, bilinear)(Sigmoid(q)); return x * psi` (attention.py:107-113), for the
+ * skip tensor x [C][Do][Ho][Wo] and the one-channel map q [D][H][W] on the coarse grid: Ho = 2 H, Wo = 2 W, Do = scale_d ? 2 D : D
+ * (D = 1, scale_d = 0: the reference's 2-D case; scale_d = 1: the 3-D net).  Up-sampling as dpi_upsample2x_fwd with linear = 1
+ * (align_corners=False, taps .25 / .75, edge-clamped).  fp32 tensors only.  x, y, dy, dx may be views at any element offset (y a channel
+ * slice of the concatenated tensor): 16-, 8- or 4-byte accesses are chosen from the addresses of the call and give bit-identical results.
+ * No atomics: every result is bitwise reproducible.
+ *   y[c][v] = x[c][v] * a[v],  a = upsample2x(s),  s = sigmoid(q);  s_out [D][H][W] receives s for the backward. */
+int dpi_attn_gate_fwd(const float* x, const float* q, int C, int D, int H, int W, int scale_d, float* s_out, float* y, void* stream);
+/* Backward of attention.py:107-113 in two launches: dx[c][v] = dy[c][v] * a[v] with t[v] = sum_c dy[c][v] * x[c][v] into ws, then
+ * dq = (adjoint up-sampling of t) * s * (1 - s) as a gather on the coarse grid.  ws: dpi_attn_gate_bwd_ws_floats floats (0 = bad geometry). */
+size_t dpi_attn_gate_bwd_ws_floats(int C, int D, int H, int W, int scale_d);
+int dpi_attn_gate_bwd(const float* dy, const float* x, const float* s, int C, int D, int H, int W, int scale_d, float* dx, float* dq,
+                      float* ws, void* stream);
+
 /* ---------------------------------------------------------------- plain 2-D UNet extras ----------
  * Replaces nn.MaxPool2d(2, 2) (unet.py:42) and nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) (unet.py:59) with
  * their backward passes.  x: [C][H][W]; pooled / transposed outputs are [C][H/2][W/2] and [Cout][2H][2W];
