@@ -85,6 +85,14 @@ SIGNATURES = {
     "dpi_attn_gate_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dpi_attn_gate_bwd_ws_floats": (_Z, [_I, _I, _I, _I, _I]),
     "dpi_attn_gate_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    # the partial convolution of --net part, partial_unet.py:42-70: (x, m, Cin, Cm, V, xm, msum, stream), (c, msum, bias|NULL, Cout, D, H, W, y,
+    # new_mask, S, stream), (Cout, V), (dy, S, Cout, V, dc, dbias|NULL, ws, stream) and (dxm, x, m, Cin, Cm, V, dx, dm|NULL, stream).
+    # ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_pconv_mask_fwd": (_I, [_P, _P, _I, _I, _Z, _P, _P, _P]),
+    "dpi_pconv_norm_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dpi_pconv_norm_bwd_ws_floats": (_Z, [_I, _Z]),
+    "dpi_pconv_norm_bwd": (_I, [_P, _P, _I, _Z, _P, _P, _P, _P]),
+    "dpi_pconv_mask_bwd": (_I, [_P, _P, _P, _I, _I, _Z, _P, _P, _P]),
     "dpi_maxpool2x2_fwd": (_I, [_P, _I, _I, _I, _P, _P]),
     "dpi_maxpool2x2_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "dpi_deconv4x4s2_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib, ops
 from . import utils as u
-from .architectures import get_net
+from .architectures import build_net
 from .data import extract_patches
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
 from .parameter import check_out_ema, net_args_are_same, parse_arguments
@@ -247,6 +247,19 @@ class Interpolator:
         h = self._holdout_dev.reshape((1, self.mask_.shape[1], 1) + tuple(self.mask_.shape[3:]))
         return self.mask_ * (1 - h)
 
+    def net_forward(self, z):
+        """The one place the network is called.  --net part takes the mask of known samples beside its input (the reference calls net(input_),
+        main.py:159, which its PartialUNet.forward(x, mask) cannot serve): training_mask(), so held-out traces are holes for the net too, as one
+        channel (amax over dim 1: the 2.5-D slab's channels; in 3-D the mask itself).  Constant per patch: built once, so a captured
+        iteration replays it unchanged."""
+        if getattr(self.args, "net", "multiunet") != "part":
+            return self.net(z)
+        src = getattr(self, "_net_mask_src", None)
+        if src is None or src[0] is not self.mask_ or src[1] is not self._holdout_dev:
+            self._net_mask = self.training_mask().amax(dim=1, keepdim=True).contiguous()          # (draws the hold-out split if the patch has none yet)
+            self._net_mask_src = (self.mask_, self._holdout_dev)
+        return self.net(z, self._net_mask)
+
     def release_packed_weights(self):
         """Hand the packed-weight scratch slots of this Interpolator's network back to the library (dpi_pack_forget, ABI 402): the bf16
         arithmetic modes keep one slot per (weight tensor, shape) and every patch builds a new network (reference main.py:286), so a
@@ -269,10 +282,10 @@ class Interpolator:
         if len(self.args.netdir) != 0:
             saved = u.read_args(os.path.join("./results", *netpath.split("/")[:-1], "args.txt"))
             assert net_args_are_same(self.args, saved)
-            self.net = get_net(saved, self.outchannel)
+            self.net = build_net(saved, self.outchannel)
             self.net.load_state_dict(torch.load(os.path.join("./results", netpath), map_location="cpu"))
         else:
-            self.net = get_net(self.args, self.outchannel)
+            self.net = build_net(self.args, self.outchannel)
             u.init_weights(self.net, self.args.inittype, self.args.initgain)
         self.net = self.net.float().to(self.device)
         self._storage_ok = None
@@ -387,6 +400,10 @@ class Interpolator:
         20.2 ms with the side stream against 18.9 without (per-node joins) and kept it off; with the round-5 schedule the order is
         reversed — 15.8-16.1 ms eager with it, 16.2 ms replayed from a graph without, 17.1-17.3 eager without; configs[4] (512x256x256
         patches) 8.4-8.8 against 8.2 it/s — so it is on for every storage type."""
+        if getattr(self.args, "net", "multiunet") == "part":
+            # every `down` convolution of the partial-convolution net is used twice (on the tensor and on the hole map): autograd ACCUMULATES its
+            # weight gradient on the main stream, which a side stream that has not run yet cannot feed (ops._deferred)
+            return False
         big = int(np.prod(self.img.shape[:-1])) >= (1 << 20)
         if os.environ.get("DPI_FORCE_OVERLAP") in ("0", "1"):       # A/B knob
             return big and os.environ["DPI_FORCE_OVERLAP"] == "1"
@@ -427,7 +444,7 @@ class Interpolator:
             _lib.check(_lib.load().dpi_axpy(float(self.add_data_weight[self.iiter]), _lib.ptr(self.add_data_), input_.numel(),
                                             _lib.ptr(input_), _lib.stream()), "dpi_axpy")
             self.input_list.append(u.torch_to_np(input_, True))
-        out_ = self.net(input_)
+        out_ = self.net_forward(input_)
         if self.is_sampler():
             self._moments_update(out_)
         ema = self._ema_pass(out_) if self.out_ema > 0.0 else None
@@ -643,7 +660,7 @@ class Interpolator:
         def _one_iteration():
             ops.begin_iteration()
             opt.zero_grad()
-            out_ = self.net(self.perturbed_input())
+            out_ = self.net_forward(self.perturbed_input())
             if self.is_sampler():
                 self._moments_update(out_)
             ema = self._ema_pass(out_) if ema_on else None

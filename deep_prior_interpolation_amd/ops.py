@@ -1444,6 +1444,72 @@ class AttentionGateFn(torch.autograd.Function):
         return dskip, dq, dg, None
 
 
+class PartialConvFn(torch.autograd.Function):
+    """Partial2DConv / Partial3DConv.forward up to its BatchNorm (reference partial_unet.py:42-70, 119-147) as one node:
+         xm = x * m;  c = conv3x3(x3)(xm, w), no bias;  S = window-and-channel sum of m;  y = S == 0 ? 0 : c / S + b;  new_mask = S != 0
+    m has x's channels or one (broadcast).  Returns (y, new_mask) with new_mask ONE channel (the reference's Cout channels are identical) and
+    not differentiable; S carries no gradient (no_grad in the reference).  The convolution, its backward-data and backward-weight are the
+    existing launches on (xm, dc), so --precision bf16mm | split reach them through the descriptor; everything else is fp32.
+    Saved for the backward: xm (the backward-weight launch reads it; rebuilding it would cost the pass over x and m again, 3 Cin V floats, for
+    Cin V floats of memory), m (dx = dxm * m), S, w — and x only where the mask needs a gradient (dm = dxm * x: every level below the first)."""
+
+    @staticmethod
+    def forward(ctx, x, m, w, b):
+        x, m, w = _req(x, "partial-conv input"), _req(m, "partial-conv mask"), _req(w, "partial-conv weight")
+        b = _req(b, "partial-conv bias") if b is not None else None
+        Cin, D, H, W = _dims(x)
+        Cm = _dims(m)[0]
+        if m.ndim != x.ndim or _dims(m)[1:] != (D, H, W) or Cm not in (1, Cin):
+            raise ValueError("partial_conv: input %s, mask %s: the mask needs the input's grid and its channels or one" % (tuple(x.shape), tuple(m.shape)))
+        if w.ndim != x.ndim or any(k != 3 for k in w.shape[2:]):
+            raise NotImplementedError("partial_conv: only the 3x3(x3) stride-1 layer (sample='none-3') has a kernel, got weight %s" % (tuple(w.shape),))
+        L = _lib.load()
+        V = D * H * W
+        xm = torch.empty_like(x)
+        msum = torch.empty(V, dtype=torch.float32, device=x.device)
+        check(L.dpi_pconv_mask_fwd(ptr(x), ptr(m), Cin, Cm, V, ptr(xm), ptr(msum), stream()), "dpi_pconv_mask_fwd")
+        d = make_desc(xm, w, 1)
+        y = torch.empty(_like_spatial(x, d.Cout, D, H, W), dtype=torch.float32, device=x.device)
+        raw_conv_fwd(d, xm, None, w, None, y)
+        new_mask = torch.empty(_like_spatial(x, 1, D, H, W), dtype=torch.float32, device=x.device)
+        S = torch.empty(V, dtype=torch.float32, device=x.device)
+        check(L.dpi_pconv_norm_fwd(ptr(y), ptr(msum), ptr(b), d.Cout, D, H, W, ptr(y), ptr(new_mask), ptr(S), stream()), "dpi_pconv_norm_fwd")
+        ctx.save_for_backward(xm, m, S, w, x if ctx.needs_input_grad[1] else None)
+        ctx.d = d
+        ctx.geo = (Cin, Cm, V)
+        ctx.has_bias = b is not None
+        ctx.mark_non_differentiable(new_mask)
+        return y, new_mask
+
+    @staticmethod
+    def backward(ctx, dy, _dnew_mask):
+        xm, m, S, w, x = ctx.saved_tensors
+        d = ctx.d
+        Cin, Cm, V = ctx.geo
+        dy = _req(dy, "partial-conv grad")
+        L = _lib.load()
+        dc = torch.empty_like(dy)
+        db = ws = None
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = torch.empty(d.Cout, dtype=torch.float32, device=dy.device)
+            ws = torch.empty(L.dpi_pconv_norm_bwd_ws_floats(d.Cout, V), dtype=torch.float32, device=dy.device)
+        check(L.dpi_pconv_norm_bwd(ptr(dy), ptr(S), d.Cout, V, ptr(dc), ptr(db), ptr(ws), stream()), "dpi_pconv_norm_bwd")
+        dx = dm = dw = None
+        if ctx.needs_input_grad[2]:
+            dw = torch.empty_like(w)
+            conv_bwd_weight_async(d, xm, None, dc, dw)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dx = torch.empty_like(xm)
+            raw_conv_bwd_data(d, dc, w, dx)                    # dxm, turned into dx in place
+            if ctx.needs_input_grad[1]:
+                dm = torch.empty_like(m)
+            check(L.dpi_pconv_mask_bwd(ptr(dx), ptr(x), ptr(m), Cin, Cm, V, ptr(dx), ptr(dm), stream()), "dpi_pconv_mask_bwd")
+            if not ctx.needs_input_grad[0]:
+                dx = None
+        join_weight_grads()
+        return dx, dm, dw, db
+
+
 class MaskedLossFn(torch.autograd.Function):
     """loss_fn(out*mask, img*mask) of main.py:161 with the SNR / PCORR sums of main.py:166-167 in the same pass.
     Returns (loss, metrics) with metrics = device double[8] {loss, snr_dB, pcorr, ...}."""
@@ -1638,6 +1704,12 @@ def attention_gate(skip, q, g, mode="nearest"):
     if mode not in ("nearest", "bilinear", "trilinear", "linear"):
         raise NotImplementedError("upsample mode %r" % mode)
     return AttentionGateFn.apply(skip, q, g, mode != "nearest")
+
+
+def partial_conv(x, m, w, b=None):
+    """(y, new_mask) of a partial convolution (PartialConvFn).  x: (1, Cin, [D,] H, W); m: x's shape or one channel; w: (Cout, Cin, [3,] 3, 3);
+    new_mask: (1, 1, [D,] H, W), no gradient."""
+    return PartialConvFn.apply(x, m, w, b)
 
 
 def masked_loss(out, img, mask, kind="mae"):

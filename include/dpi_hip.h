@@ -316,6 +316,29 @@ size_t dpi_attn_gate_bwd_ws_floats(int C, int D, int H, int W, int scale_d);
 int dpi_attn_gate_bwd(const float* dy, const float* x, const float* s, int C, int D, int H, int W, int scale_d, float* dx, float* dq,
                       float* ws, void* stream);
 
+/* ---------------------------------------------------------------- partial convolution ------------
+ * Replaces everything around the convolution in Partial2DConv / Partial3DConv.forward (partial_unet.py:42-70, 119-147) for one patch:
+ *   xm = x * m;  c = conv3x3(x3)(xm, W) without bias (dpi_conv_fwd);  S[v] = sum over the channels and the zero-padded 3x3(x3) window of m
+ *   (the all-ones mask_conv, one value per voxel);  y[o][v] = S[v] == 0 ? 0 : c[o][v] / S[v] + b[o];  new_mask[v] = S[v] == 0 ? 0 : 1.
+ * x [Cin][V], m [Cm][V] with Cm = Cin or 1 (broadcast), V = D H W voxels (D = 1: 2-D, the window is 3 x 3).  S is not differentiated
+ * (partial_unet.py:47-49 computes it under no_grad).  fp32 tensors only.  Tensors may be views at any element offset and V any count:
+ * 16-, 8- or 4-byte accesses are chosen from the addresses of the call and from V and give bit-identical results.  No atomics: every
+ * result, the bias gradient included, is bitwise reproducible.
+ *   partial_unet.py:44,121 `input_x * mask` and the channel sum of the mask: xm [Cin][V], msum[v] = sum_c m[c][v] (Cm = 1: Cin * m[v]) */
+int dpi_pconv_mask_fwd(const float* x, const float* m, int Cin, int Cm, size_t V, float* xm, float* msum, void* stream);
+/* partial_unet.py:47-70, 124-147: S = box sum of msum (27 additions in the order d, h, w, a tap outside adding 0), y (may be c itself),
+ * the ONE-channel new_mask [V] (the reference stores Cout identical channels) and S [V] for the backward.  bias [Cout] or NULL. */
+int dpi_pconv_norm_fwd(const float* c, const float* msum, const float* bias, int Cout, int D, int H, int W, float* y, float* new_mask,
+                       float* S, void* stream);
+/* Backward of partial_unet.py:65-66, 142-143: dc[o][v] = S[v] == 0 ? 0 : dy[o][v] / S[v]; dbias[o] = sum over S[v] != 0 of dy[o][v] (NULL:
+ * not computed) as one partial per 256 voxels in ws, then a fixed-order finaliser.  ws: dpi_pconv_norm_bwd_ws_floats floats (0 = bad
+ * geometry), needed only with dbias. */
+size_t dpi_pconv_norm_bwd_ws_floats(int Cout, size_t V);
+int dpi_pconv_norm_bwd(const float* dy, const float* S, int Cout, size_t V, float* dc, float* dbias, float* ws, void* stream);
+/* Backward of partial_unet.py:44,121 `input_x * mask`: dx[c][v] = dxm[c][v] * m[c][v] (dx may be dxm itself); dm (NULL: not computed)
+ * [Cm][V]: dm[c][v] = dxm[c][v] * x[c][v] for Cm = Cin, dm[v] = sum_c dxm[c][v] * x[c][v] for Cm = 1.  x may be NULL without dm. */
+int dpi_pconv_mask_bwd(const float* dxm, const float* x, const float* m, int Cin, int Cm, size_t V, float* dx, float* dm, void* stream);
+
 /* ---------------------------------------------------------------- plain 2-D UNet extras ----------
  * Replaces nn.MaxPool2d(2, 2) (unet.py:42) and nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) (unet.py:59) with
  * their backward passes.  x: [C][H][W]; pooled / transposed outputs are [C][H/2][W/2] and [Cout][2H][2W];
