@@ -123,6 +123,10 @@ SIGNATURES = {
     "dpi_dips": (_I, [_P, _P, _P, _Z, _P, _P, _P]),
     "dpi_hale_sections": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),                     # ABI 405: the add-on on 3-D patches
     "dpi_structure_tensor_sections": (_I, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
+    # --avo_theta, operators/avo.py:67-95: (x, G, ntheta, T, S, y, stream) and (y, G, ntheta, T, S, x, stream).  ABI_VERSION stays: a stale
+    # library fails on the unresolved symbols
+    "dpi_avo_fwd": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
+    "dpi_avo_adj": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
     "dpi_max_ws_floats": (_Z, [_Z]),
     "dpi_scaled_max": (_I, [_P, _Z, _F, _P, _P, _P]),
     "dpi_threshold": (_I, [_P, _Z, _P, _P, _P]),

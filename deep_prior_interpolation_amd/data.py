@@ -5,7 +5,8 @@
 unsorted glob, data.py:99 — SURVEY App. B.7).
 
 Ours, opt-in: --reassembly cover cuts (and re-assembles) one more, edge-flush window on every axis the regular grid leaves a tail on, --blend
-taper weights the overlaps (utils/patch_extractor.py); `reconstruct_patches(field="posterior_std")` blends the per-patch spread of a sampler run."""
+taper weights the overlaps (utils/patch_extractor.py); `reconstruct_patches(field="posterior_std")` blends the per-patch spread of a sampler run,
+`reconstruct_patches(field="avo_model")` re-assembles the three parameter sections of an --avo_theta run."""
 import os
 from glob import glob
 from typing import List
@@ -85,14 +86,44 @@ def extract_patches(args) -> List[dict]:
     return out
 
 
+def _reconstruct_avo_model(args, results_root):
+    """The windows of the (T, X, ntheta) volume with the angle axis swapped for the three parameter sections: the same origins and, under
+    --blend taper, the same ramps along t and x (the last axis is one whole window either way)."""
+    cover, blend = reassembly_flags(args)
+    inputs = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
+    pe = patch_extractor_for(inputs.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
+    if args.datadim != "2.5d" or args.slice != "tx" or inputs.ndim != 3 or pe.dim[-1] != inputs.shape[-1]:
+        raise ValueError("field avo_model belongs to an --avo_theta run: --datadim 2.5d --slice tx on a (T, X, ntheta) volume whose angle "
+                         "axis is one window (--imgchannel %r against %r angles)" % (args.imgchannel, inputs.shape[-1]))
+    files = sorted((p for p in glob(os.path.join(results_root, args.outdir) + "/*.npy") if "output" not in os.path.basename(p)),
+                   key=lambda p: os.path.basename(p))
+    outs = []
+    for path in files:
+        rec = np.load(path, allow_pickle=True).item()
+        if "avo_theta" not in rec:
+            raise ValueError("%s holds no avo_model: not the result of an --avo_theta run" % path)
+        v = rec.get("avo_model")
+        outs.append(np.asarray(v) if v is not None else np.zeros(tuple(pe.dim[:-1]) + (3,), dtype=np.float32))
+    in_size, dim, stride = tuple(inputs.shape[:-1]) + (3,), tuple(pe.dim[:-1]) + (3,), tuple(pe.stride[:-1]) + (3,)
+    origins = u.window_origins(in_size, dim, stride, cover=cover)
+    if len(outs) != len(origins):
+        raise ValueError("%d result files for %d windows" % (len(outs), len(origins)))
+    return u.reassemble(np.asarray(outs).reshape((-1,) + dim), origins, u.reassembled_shape(in_size, dim, stride, cover), dim, stride,
+                        blend) / args.gain
+
+
 def reconstruct_patches(args, return_history=False, verbose=False, results_root="./results", field="output"):
     """Re-assemble the volume from ./results/<outdir>/<name>_run.npy (data.py:87-130).
 
     field = "posterior_std" (a sampler run, --optimizer sgld | psgld) blends the per-patch spread instead:
     sqrt(sum(w sigma^2) / sum(w)) / |gain|, a patch without one (skipped, or fewer than two samples) counting as 0.  --reassembly cover
-    returns the input's shape, --blend taper weights the overlaps; with the defaults and field = "output" nothing differs from before."""
-    if field not in ("output", "posterior_std"):
-        raise ValueError("field must be output or posterior_std, got %r" % (field,))
+    returns the input's shape, --blend taper weights the overlaps; with the defaults and field = "output" nothing differs from before.
+    field = "avo_model" (an --avo_theta run) re-assembles the per-patch parameter sections (T, X, 3) into (T', X', 3) with the same windows
+    and weights along t and x, divided by gain (the model is linear in the data); a skipped patch counts as zeros."""
+    if field not in ("output", "posterior_std", "avo_model"):
+        raise ValueError("field must be output, posterior_std or avo_model, got %r" % (field,))
+    if field == "avo_model":
+        return _reconstruct_avo_model(args, results_root)
     cover, blend = reassembly_flags(args)
     inputs = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     pe = patch_extractor_for(inputs.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)

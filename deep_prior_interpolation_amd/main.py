@@ -16,7 +16,7 @@ from . import utils as u
 from .architectures import build_net
 from .data import extract_patches
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import check_out_ema, net_args_are_same, parse_arguments
+from .parameter import check_avo, check_out_ema, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -45,6 +45,9 @@ class Interpolator:
         self.out_ema = check_out_ema(args)
         self._ema_avg = self._ema_best = self._ema_one = None    # per patch: the average, its selected snapshot, a constant 1 flag
         self.ema_min = None
+        # --avo_theta (ours): the net outputs three elastic-parameter sections, the AVO operator maps them to the angle sections (net_forward)
+        self.avo = check_avo(args)                               # None, or (theta, vsvp, linearization)
+        self._avo_op = None                                      # built per patch length T (net_forward)
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
         self.optimizer_kind = getattr(args, "optimizer", "adam")
         if self.optimizer_kind not in ("adam", "sgld", "psgld"):
@@ -251,7 +254,33 @@ class Interpolator:
         """The one place the network is called.  --net part takes the mask of known samples beside its input (the reference calls net(input_),
         main.py:159, which its PartialUNet.forward(x, mask) cannot serve): training_mask(), so held-out traces are holes for the net too, as one
         channel (amax over dim 1: the 2.5-D slab's channels; in 3-D the mask itself).  Constant per patch: built once, so a captured
-        iteration replays it unchanged."""
+        iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
+        them to the patch's angle sections: what this returns is a data-domain tensor either way."""
+        if self.avo is not None:
+            return self._avo_operator(int(z.shape[2]))(self._net_forward(z))
+        return self._net_forward(z)
+
+    def _avo_operator(self, nt0):
+        """--avo_theta: the operator of the loaded patch (nt0 = its T), built once and kept while T stays the same; its coefficients are
+        uploaded at its first call, i.e. in the eager iteration 0 of a captured run."""
+        if self._avo_op is None or self._avo_op.nt0 != nt0:
+            from .operators import AVOLinearModelling
+            theta, vsvp, lin = self.avo
+            self._avo_op = AVOLinearModelling(theta, vsvp=vsvp, nt0=nt0, spatdims=(1,), linearization=lin)
+        return self._avo_op
+
+    def avo_model(self):
+        """--avo_theta: the three parameter sections (T, X, 3) behind the selected output, m_t = pinv(G_t) out_best_t per time sample in
+        float64 with the fp32 G of the device, stored as fp32.  Every selected output — the best iterate, the running average, the posterior
+        mean — is a linear combination of iterates G m_i, so this returns the same combination of the m_i: no second tracking path on the
+        device.  None for a patch that was not optimised."""
+        if self.avo is None or self._out_best_dev is None or self.out_best is None:
+            return None
+        from .operators import avo_model_from_data
+        op = self._avo_operator(int(self.out_best.shape[0]))
+        return avo_model_from_data(self.out_best, op.G.numpy().reshape(op.ntheta, 3, op.nt0)).astype(np.float32)
+
+    def _net_forward(self, z):
         if getattr(self.args, "net", "multiunet") != "part":
             return self.net(z)
         src = getattr(self, "_net_mask_src", None)
@@ -275,6 +304,10 @@ class Interpolator:
         self._graph = None            # a captured iteration of the old network holds the slot addresses: it must not be replayed again
         return n
 
+    def net_outchannel(self):
+        """Channels the network itself writes: the patch's, or with --avo_theta the three parameter sections."""
+        return 3 if self.avo is not None else self.outchannel
+
     def build_model(self, netpath=None):
         self.release_packed_weights()
         if self.outchannel is None:
@@ -282,10 +315,10 @@ class Interpolator:
         if len(self.args.netdir) != 0:
             saved = u.read_args(os.path.join("./results", *netpath.split("/")[:-1], "args.txt"))
             assert net_args_are_same(self.args, saved)
-            self.net = build_net(saved, self.outchannel)
+            self.net = build_net(saved, self.net_outchannel())
             self.net.load_state_dict(torch.load(os.path.join("./results", netpath), map_location="cpu"))
         else:
-            self.net = build_net(self.args, self.outchannel)
+            self.net = build_net(self.args, self.net_outchannel())
             u.init_weights(self.net, self.args.inittype, self.args.initgain)
         self.net = self.net.float().to(self.device)
         self._storage_ok = None
@@ -780,6 +813,8 @@ class Interpolator:
         if self.out_ema > 0.0:
             run["out_ema"] = self.out_ema                        # `output` is the selected running average, best_iter its iteration
             run["best_iter"] = self.best_iter
+        if self.avo is not None:
+            run.update(avo_theta=list(self.avo[0]), avo_vsvp=self.avo[1], avo_linearization=self.avo[2], avo_model=self.avo_model())
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)

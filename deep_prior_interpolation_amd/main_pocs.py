@@ -34,6 +34,9 @@ class Interpolator(_Base):
         if (getattr(args, "out_ema", 0.0) or 0.0) != 0.0:
             raise ValueError("main_pocs does not support --out_ema (got %g): the POCS target follows the current output, an average of "
                              "outputs has no target of its own to be measured against; run main.py" % args.out_ema)
+        if getattr(args, "avo_theta", None) is not None:
+            raise ValueError("main_pocs does not support --avo_theta: the POCS projection thresholds the spectrum of a section, which knows "
+                             "nothing of the three-parameter subspace the AVO operator confines the output to; run main.py")
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

@@ -602,12 +602,17 @@ def main(argv=None):
         rec = reconstruct_patches(args) if rank == 0 else None
         if rank == 0 and sampler:
             volumes["std"] = reconstruct_patches(args, field="posterior_std")
+        if rank == 0 and getattr(args, "avo_theta", None) is not None:
+            volumes["avo"] = reconstruct_patches(args, field="avo_model")
     _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
         if sampler and volumes.get("std") is not None:
             # the window-weighted mean of the per-patch posterior variances, as a std: the spread WITHIN the windows
             np.save(os.path.join(outpath, "reconstructed_std.npy"), volumes["std"])
+        if volumes.get("avo") is not None:
+            # --avo_theta: the three parameter sections (T', X', 3) behind reconstructed.npy, re-assembled with the same windows
+            np.save(os.path.join(outpath, "reconstructed_avo.npy"), volumes["avo"])
         print("rank 0: %d patches total, %d local; reconstructed volume %s saved" % (len(patches), len(mine), rec.shape))
     if world > 1:
         dist.destroy_process_group()

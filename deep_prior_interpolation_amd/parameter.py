@@ -120,6 +120,15 @@ _FLAGS = [
     (("--blend",), dict(type=str, required=False, default="flat", choices=["flat", "taper"],
                        help="ours: flat = overlapping patches are averaged (reference); taper = weighted by sin^2 ramps over the overlap, "
                             "which removes the step at every window edge")),
+    # AVO-constrained interpolation of angle gathers (ours: the reference ships operators/avo.py without a caller)
+    (("--avo_theta",), dict(nargs="+", type=float, required=False,
+                           help="ours: incidence angles in degrees of a (T, X, ntheta) volume of angle gathers (absent = off).  The network "
+                                "then outputs three elastic-parameter sections and the linearised AVO operator maps them to the ntheta angle "
+                                "sections the loss sees; needs --datadim 2.5d --slice tx --imgchannel ntheta.  The parameter sections are "
+                                "saved as avo_model")),
+    (("--avo_vsvp",), dict(type=float, required=False, default=0.5, help="ours: vs/vp ratio of the AVO coefficients (--avo_theta)")),
+    (("--avo_linearization",), dict(type=str, required=False, default="akirich", choices=["akirich", "fatti"],
+                                   help="ours: Aki-Richards or Fatti form of the AVO coefficients (--avo_theta)")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -154,7 +163,41 @@ def postprocess(args: Namespace) -> Namespace:
         raise ValueError("--holdout must lie in [0, 0.5], got %r" % args.holdout)
     _postprocess_sampler(args)
     check_out_ema(args)
+    check_avo(args)
     return args
+
+
+def check_avo(args: Namespace):
+    """--avo_theta and what it needs; returns None when it is off (also for a Namespace without the key, as those of older args.txt files),
+    else (theta list, vsvp, linearization)."""
+    theta = getattr(args, "avo_theta", None)
+    if theta is None:
+        return None
+    theta = [float(t) for t in theta]
+    vsvp = float(getattr(args, "avo_vsvp", 0.5))
+    lin = getattr(args, "avo_linearization", "akirich")
+    if args.datadim != "2.5d" or args.slice != "tx":
+        raise ValueError("--avo_theta needs --datadim 2.5d --slice tx (a (T, X, ntheta) volume whose stacked channel axis is the angle "
+                         "axis), got --datadim %s --slice %s" % (args.datadim, args.slice))
+    if args.imgchannel != len(theta):
+        raise ValueError("--avo_theta names %d angles: --imgchannel must be %d, got %r" % (len(theta), len(theta), args.imgchannel))
+    if len(set(theta)) < 3:
+        raise ValueError("--avo_theta needs at least 3 distinct angles for the three parameter sections, got %r" % (theta,))
+    if not vsvp > 0.0:
+        raise ValueError("--avo_vsvp must be > 0, got %r" % (vsvp,))
+    if lin not in ("akirich", "fatti"):
+        raise ValueError("--avo_linearization must be akirich or fatti, got %r" % (lin,))
+    import numpy as np
+    from .operators.avo import avo_coefficients
+    try:
+        G = avo_coefficients(theta, vsvp, 1, lin)[:, :, 0]
+    except ValueError as e:
+        raise ValueError("--avo_theta: %s" % e) from e
+    if np.linalg.matrix_rank(G) < 3:
+        raise ValueError("--avo_theta %r with --avo_vsvp %g gives coefficients of rank %d: the three parameter sections cannot be told "
+                         "apart (angles of equal sin^2 count once)" % (theta, vsvp, int(np.linalg.matrix_rank(G))))
+    args.avo_theta = theta
+    return theta, vsvp, lin
 
 
 def check_out_ema(args: Namespace) -> float:
@@ -207,6 +250,10 @@ def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
     """Compatibility of a saved args.txt with the current run before loading its weights (parameter.py:133-173)."""
     a, b = vars(args1), vars(args2)
     errors = [k for k in _MUST_MATCH if a[k] != b[k]]
+    # --avo_theta (ours) decides the network's output channels and what they mean; args.txt files of older runs lack the key: off
+    ta, tb = a.get("avo_theta"), b.get("avo_theta")
+    if (None if ta is None else [float(t) for t in ta]) != (None if tb is None else [float(t) for t in tb]):
+        errors.append("avo_theta")
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

@@ -15,7 +15,7 @@ down to a quarter), so that (128, 64, 64) or (48, 32, 32) stand-ins hold as many
 bench patch): kept because committed reference recordings (`tests/golden/plateau_96x64x64.npz`) were made on it."""
 import numpy as np
 
-__all__ = ["hyperbolic_volume", "tiled_hyperbolic_volume", "sparse_hyperbolic_volume", "random_trace_mask", "coarse_std"]
+__all__ = ["hyperbolic_volume", "tiled_hyperbolic_volume", "sparse_hyperbolic_volume", "random_trace_mask", "coarse_std", "avo_gathers"]
 
 TARGET_RMS = 0.19          # std of the un-gained cube: 40 * 0.19 * sqrt(0.34) = 4.4, the middle of the notebook's 3.94 .. 5.16
 
@@ -88,6 +88,22 @@ def sparse_hyperbolic_volume(shape, seed=0, nev=5, dtype=np.float32):
         a = (np.pi * 0.25 * (t - tt)) ** 2
         vol += (amp * (1.0 - 2.0 * a) * np.exp(-a)).astype(np.float32)
     return (vol / np.abs(vol).max()).astype(dtype)
+
+
+def avo_gathers(shape, theta, vsvp=0.5, seed=0, linearization="akirich", return_model=False, dtype=np.float32):
+    """Stand-in for a pre-stack line (--avo_theta): a (T, X, ntheta) volume of angle gathers that obeys the linearised AVO equation
+    exactly.  Three independent parameter sections (T, X) — the x-y plane 0 of `hyperbolic_volume((T, X, 1))` with the seeds 3 seed,
+    3 seed + 1, 3 seed + 2: smooth hyperbolic events — are pushed through the float64 coefficients G(theta, vsvp) of
+    operators/avo.py, d[t, x, a] = sum_k G[a, k] m_k[t, x], and rounded once to `dtype`.  return_model=True also gives the model
+    (T, X, 3) in float64."""
+    from ..operators.avo import avo_coefficients
+    nt, nx = int(shape[0]), int(shape[1])
+    if len(shape) == 3 and int(shape[2]) != len(theta):
+        raise ValueError("shape %r names %d angle sections for %d angles" % (tuple(shape), shape[2], len(theta)))
+    model = np.stack([hyperbolic_volume((nt, nx, 1), seed=3 * int(seed) + k, dtype=np.float64)[:, :, 0] for k in range(3)], axis=-1)
+    G = avo_coefficients(theta, vsvp, 1, linearization)[:, :, 0]                  # (ntheta, 3)
+    data = np.einsum("ak,txk->txa", G, model).astype(dtype)
+    return (data, model) if return_model else data
 
 
 def random_trace_mask(shape, rate, seed=0, dtype=np.float32):

@@ -528,6 +528,18 @@ int dpi_hale_sections(const float* x, const float* coef, int C, int T, int X, in
 int dpi_structure_tensor_sections(const float* x, int C, int T, int X, int Y, float dt, float dx, float dy, float* gtt, float* gtx,
                                   float* gxx, float* gty, float* gyy, void* stream);
 
+/* ---------------------------------------------------------------- AVO modelling (--avo_theta) -------
+ * Replaces operators/avo.py:67-95 AVOLinearModelling.forward / .adjoint: the linearised amplitude-versus-angle operator that maps three
+ * elastic-parameter sections to ntheta angle sections, y[a][t][s] = sum_k G[a][k][t] * x[k][t][s] (dpi_avo_fwd), and its exact transpose
+ * x[k][t][s] = sum_a G[a][k][t] * y[a][t][s] (dpi_avo_adj: the backward of the forward call and the reference's .adjoint).
+ * x = [3][T][S], y = [ntheta][T][S], G = [ntheta][3][T] (the reference's G (ntheta, 3, nt0, 1[, 1]) without its unit axes), all fp32 and
+ * contiguous; S = the product of the spatial sizes behind t.  Any ntheta, T, S >= 1 and any 4-byte aligned x / y (16-byte accesses only
+ * on the rows that start on 16 bytes in both); no atomics: the sums run in a fixed order (k = 0, 1, 2; a = 0 .. ntheta-1), so a result
+ * does not depend on the launch shape.  Input and output must not alias.  ABI version stays: a stale library fails on the unresolved
+ * symbols. */
+int dpi_avo_fwd(const float* x, const float* G, int ntheta, int T, size_t S, float* y, void* stream);
+int dpi_avo_adj(const float* y, const float* G, int ntheta, int T, size_t S, float* x, void* stream);
+
 /* ---------------------------------------------------------------- POCS regulariser --------------
  * Replaces utils/pocs.py:5-19 (threshold / compute_threshold: out = max(x) * scale with scale = perc/100, kept on the device;
  * y = x * ((x > th) + (x < -th)) on the real view of the spectrum) and :80-84 (y = weighted_data + weighted_mask * x).

@@ -1,0 +1,267 @@
+"""--avo_theta on the GPU: dpi_avo_fwd / dpi_avo_adj against float64 and against the reference's recorded vectors (tests/golden/avo.npz),
+the dot test, autograd, and the deep-prior loop with the operator behind the network (eager and captured).  Shapes are (ntheta, T, S)."""
+import os
+from argparse import Namespace
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import jstr
+
+from deep_prior_interpolation_amd import _lib, utils as u
+from deep_prior_interpolation_amd.operators import AVOLinearModelling, dottest
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+U24 = 2.0 ** -24
+
+# the issue's shapes, then ours: rows that start on 16 bytes with a tail behind the vectors in a second workgroup (8, 4, 1030), all rows
+# aligned and no tail over three workgroups (6, 2, 2052), the smallest problem, and more time samples than one grid axis holds
+SHAPES = [(3, 8, (5,)), (5, 37, (19,)), (4, 16, (7, 9)), (8, 5, (1030,)),
+          (8, 4, (1030,)), (6, 2, (2052,)), (1, 1, (1,)), (3, 65600, (2,))]
+IDS = ["x".join(str(n) for n in (a, t) + s) for a, t, s in SHAPES]
+
+
+def _op(ntheta, T, spat, lin="akirich"):
+    theta = np.linspace(0.0, 45.0, ntheta) if ntheta > 1 else np.array([20.0])
+    return AVOLinearModelling(theta.tolist(), vsvp=torch.linspace(0.4, 0.6, T), nt0=T, spatdims=spat, linearization=lin)
+
+
+def _vectors(ntheta, T, spat, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randn((1, 3, T) + spat, generator=gen), torch.randn((1, ntheta, T) + spat, generator=gen)
+
+
+def _g64(op):
+    return op.G.numpy().reshape(op.ntheta, 3, op.nt0).astype(np.float64)          # the fp32 coefficients the device holds
+
+
+def _fwd64(G, x):
+    """(exact result, sum_k |G_k x_k|) for x (1, 3, T, *spat), both (1, ntheta, T, *spat)."""
+    xs = x.numpy().astype(np.float64).reshape(3, G.shape[2], -1)
+    shape = (1, G.shape[0]) + tuple(x.shape[2:])
+    return np.einsum("akt,kts->ats", G, xs).reshape(shape), np.einsum("akt,kts->ats", np.abs(G), np.abs(xs)).reshape(shape)
+
+
+def _adj64(G, y):
+    ys = y.numpy().astype(np.float64).reshape(G.shape[0], G.shape[2], -1)
+    shape = (1, 3) + tuple(y.shape[2:])
+    return np.einsum("akt,ats->kts", G, ys).reshape(shape), np.einsum("akt,ats->kts", np.abs(G), np.abs(ys)).reshape(shape)
+
+
+def _check(got, ref, bound, what):
+    err = np.abs(got.detach().cpu().numpy().astype(np.float64) - ref)
+    worst = float((err / np.maximum(bound, 1e-300)).max())
+    print("%s: worst error / bound = %.3f" % (what, worst))
+    assert got.shape == ref.shape and np.all(err <= bound), (what, worst)
+
+
+@pytest.mark.parametrize("ntheta, T, spat", SHAPES, ids=IDS)
+def test_forward_and_adjoint_against_float64(ntheta, T, spat):
+    """forward: three products and two adds, |err| <= 4 * 2^-24 * sum_k |G x|; adjoint: ntheta products and ntheta - 1 adds,
+    |err| <= (ntheta + 1) * 2^-24 * sum_a |G y|."""
+    op = _op(ntheta, T, spat)
+    x, y = _vectors(ntheta, T, spat)
+    G = _g64(op)
+    ref, mag = _fwd64(G, x)
+    _check(op.forward(x.to(DEV)), ref, 4 * U24 * mag, "forward")
+    ref, mag = _adj64(G, y)
+    _check(op.adjoint(y.to(DEV)), ref, (ntheta + 1) * U24 * mag, "adjoint")
+
+
+@pytest.mark.parametrize("off_in, off_out", [(1, 0), (1, 1), (2, 3), (0, 1)])
+def test_offset_views(off_in, off_out):
+    """(5, 37, 19) on views moved off their allocation's alignment by whole elements: through the operator (input view only) and through
+    the entry points with both tensors moved, inside guard bands that must stay untouched."""
+    ntheta, T, spat = 5, 37, (19,)
+    op = _op(ntheta, T, spat)
+    x, y = _vectors(ntheta, T, spat, seed=1)
+    G = _g64(op)
+    L = _lib.load()
+    g_dev = torch.from_numpy(op.G.numpy().reshape(ntheta, 3, T).copy()).to(DEV)
+
+    def view(t, off):
+        buf = torch.full((t.numel() + off + 8,), 777.0, device=DEV)
+        v = buf[off:off + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == (4 * off) % 16 and v.is_contiguous()
+        return buf, v
+
+    for adjoint, src, ref_fn, k in ((False, x, _fwd64, 4), (True, y, _adj64, ntheta + 1)):
+        ref, mag = ref_fn(G, src)
+        _, vin = view(src, off_in)
+        if off_out == 0:
+            got = op.adjoint(vin) if adjoint else op.forward(vin)
+        else:
+            obuf, got = view(torch.zeros(ref.shape), off_out)
+            fn = L.dpi_avo_adj if adjoint else L.dpi_avo_fwd
+            _lib.check(fn(_lib.ptr(vin), _lib.ptr(g_dev), ntheta, T, 19, _lib.ptr(got), _lib.stream()), "dpi_avo")
+            torch.cuda.synchronize()
+            assert bool((obuf[:off_out] == 777.0).all()) and bool((obuf[off_out + got.numel():] == 777.0).all())
+        _check(got, ref, k * U24 * mag, "adjoint" if adjoint else "forward")
+
+
+def test_vector_and_element_paths_give_the_same_bits():
+    """(8, 4, 1030) has rows on 16 bytes (16-byte accesses and a tail); the same numbers on a view moved by one element take the
+    element-wise path everywhere: same sums in the same order."""
+    ntheta, T, spat = 8, 4, (1030,)
+    op = _op(ntheta, T, spat)
+    x, y = _vectors(ntheta, T, spat, seed=2)
+    for fn, src in ((op.forward, x), (op.adjoint, y)):
+        buf = torch.zeros(src.numel() + 1, device=DEV)
+        moved = buf[1:].view(src.shape)
+        moved.copy_(src)
+        assert torch.equal(fn(src.to(DEV)), fn(moved))
+
+
+def test_fixture_vectors(golden):
+    """The reference's own forward(x) / adjoint(y) on its own fp32 G: the float64 bounds above plus the recorded coefficient gap
+    (relative to max|G|) times sum_k |x_k| (forward) / sum_a |y_a| (adjoint)."""
+    g = golden("avo")
+    gap = float(g["gap_max"])
+    for name in sorted(g["vec"]):
+        v = g["vec"][name]
+        c = g["coef"]["%02d" % int(v["coef"])]
+        vsvp = float(c["vsvp"][0]) if c["vsvp"].size == 1 else torch.from_numpy(c["vsvp"])
+        x, y = torch.from_numpy(v["x"]), torch.from_numpy(v["y"])
+        op = AVOLinearModelling(c["theta"].tolist(), vsvp=vsvp, nt0=int(c["nt0"]), spatdims=tuple(x.shape[3:]), linearization=str(c["lin"]))
+        Gref = c["G"].astype(np.float64)
+        gap_abs = gap * np.abs(Gref).max()
+        _, mag = _fwd64(Gref, x)
+        sx = np.abs(v["x"].astype(np.float64)).sum(axis=1, keepdims=True)
+        _check(op.forward(x.to(DEV)), v["fwd"].astype(np.float64), 4 * U24 * mag + gap_abs * sx, "vec %s forward" % name)
+        _, mag = _adj64(Gref, y)
+        sy = np.abs(v["y"].astype(np.float64)).sum(axis=1, keepdims=True)
+        _check(op.adjoint(y.to(DEV)), v["adj"].astype(np.float64), (op.ntheta + 1) * U24 * mag + gap_abs * sy, "vec %s adjoint" % name)
+
+
+@pytest.mark.parametrize("ntheta, T, spat", SHAPES[:6], ids=IDS[:6])
+@pytest.mark.parametrize("lin", ["akirich", "fatti"])
+def test_dottest(ntheta, T, spat, lin):
+    op = _op(ntheta, T, spat, lin)
+    x, y = _vectors(ntheta, T, spat)
+    _, rel = dottest(op, x.to(DEV), y.to(DEV), verbose=False, generator=torch.Generator().manual_seed(3))
+    print("dottest relative error %.3e" % rel)
+    assert rel <= 1e-5
+
+
+def test_autograd_backward_is_the_other_kernel():
+    op = _op(5, 37, (19,))
+    x, y = _vectors(5, 37, (19,), seed=4)
+    x, y = x.to(DEV).requires_grad_(True), y.to(DEV).requires_grad_(True)
+    op.forward(x).backward(y.detach())
+    assert torch.equal(x.grad, op.adjoint(y.detach()))
+    op.adjoint(y).backward(x.detach())
+    assert torch.equal(y.grad, op.forward(x.detach()))
+
+
+def test_entry_points_refuse_bad_arguments():
+    L = _lib.load()
+    t = torch.zeros(64, device=DEV)
+    for fn in (L.dpi_avo_fwd, L.dpi_avo_adj):
+        assert fn(_lib.ptr(t), _lib.ptr(t), 0, 2, 2, _lib.ptr(t[32:]), _lib.stream()) != 0          # ntheta < 1
+        assert fn(_lib.ptr(t), _lib.ptr(t), 3, 2, 0, _lib.ptr(t[32:]), _lib.stream()) != 0          # S < 1
+        assert fn(_lib.ptr(t), _lib.ptr(t), 3, 2, 2, _lib.ptr(t), _lib.stream()) != 0               # in place
+        assert fn(None, _lib.ptr(t), 3, 2, 2, _lib.ptr(t), _lib.stream()) != 0
+
+
+# ---------------------------------------------------------------- the loop --------------------------------------------------------
+THETA = [0.0, 10.0, 20.0, 30.0, 40.0]
+
+
+def _avo_run(tmp_path, mode, extra=(), epochs=3):
+    """The tiny 2.5-D multiunet configuration of the trajectory fixtures (filters 4 8, skip 4, 8 input channels) on a 32 x 32 x 5 patch
+    of avo_gathers with half the traces removed."""
+    from deep_prior_interpolation_amd.main import Interpolator
+    from deep_prior_interpolation_amd.parameter import parse_arguments
+    a = parse_arguments(["--imgdir", "x", "--datadim", "2.5d", "--slice", "tx", "--imgchannel", "5", "--filters", "4", "8", "--skip", "4",
+                         "--inputdepth", "8", "--gain", "40", "--epochs", str(epochs), "--gpu", "0", "--avo_theta"] + [str(t) for t in THETA]
+                        + list(extra))
+    vol = u.avo_gathers((32, 32, 5), THETA, vsvp=0.5, seed=0).astype(np.float64) * a.gain
+    mask = np.broadcast_to(u.random_trace_mask((32, 32, 1), 0.5, seed=1), vol.shape).astype(np.float64)
+    out = tmp_path / (mode + "_".join(extra).replace("-", ""))
+    os.makedirs(out)
+    T = Interpolator(a, str(out))
+    T.load_data({"image": vol, "mask": mask, "name": "0"})
+    T.begin_patch(0)
+    T.build_model()
+    T.build_input()
+    T.optimize(verbose=False, mode=mode, check_every=2)
+    T.save_result()
+    run = np.load(out / "0_run.npy", allow_pickle=True).item()
+    return T, run
+
+
+def test_loop_eager_and_graph(tmp_path):
+    res = {}
+    for mode in ("eager", "graph"):
+        T, run = _avo_run(tmp_path, mode)
+        assert T.net_outchannel() == 3 and len(T.history.loss) == 3 and np.isfinite(T.history.loss).all()
+        assert run["avo_theta"] == THETA and run["avo_vsvp"] == 0.5 and run["avo_linearization"] == "akirich"
+        out, model = run["output"], run["avo_model"]
+        assert out.shape == (32, 32, 5) and model.shape == (32, 32, 3) and model.dtype == np.float32
+        # G m reproduces the output within the recovery bound, per (t, x): 8 cond(G_t) 2^-24 |m|
+        G = T._avo_op.G.numpy().reshape(5, 3, 32).astype(np.float64)
+        back = np.einsum("akt,txk->txa", G, model.astype(np.float64))
+        cond = np.array([np.linalg.cond(G[:, :, t]) for t in range(32)])
+        err = np.linalg.norm(back - out.astype(np.float64), axis=-1)
+        bound = 8.0 * cond[:, None] * U24 * np.linalg.norm(model.astype(np.float64), axis=-1)
+        print("%s: worst |G m - output| / bound = %.3f" % (mode, float((err / bound).max())))
+        assert np.all(err <= bound)
+        res[mode] = (np.array(T.history.loss), np.array(T.history.snr), out, model)
+    np.testing.assert_allclose(res["graph"][0], res["eager"][0], rtol=1e-12)
+    np.testing.assert_allclose(res["graph"][1], res["eager"][1], rtol=1e-12)
+    np.testing.assert_array_equal(res["graph"][2], res["eager"][2])
+    np.testing.assert_array_equal(res["graph"][3], res["eager"][3])
+
+
+@pytest.mark.parametrize("extra, fields", [(("--holdout", "0.2"), ("holdout", "best_iter")), (("--out_ema", "0.9"), ("out_ema", "best_iter"))])
+def test_loop_with_holdout_and_with_out_ema(tmp_path, extra, fields):
+    for mode in ("eager", "graph"):
+        T, run = _avo_run(tmp_path, mode, extra)
+        assert len(T.history.loss) == 3 and np.isfinite(T.history.loss).all()
+        for f in fields:
+            assert run[f] is not None
+        assert run["output"].shape == (32, 32, 5) and run["avo_model"].shape == (32, 32, 3) and np.isfinite(run["avo_model"]).all()
+
+
+def test_skipped_patch_has_no_model(tmp_path):
+    from deep_prior_interpolation_amd.main import Interpolator
+    from deep_prior_interpolation_amd.parameter import parse_arguments
+    a = parse_arguments(["--imgdir", "x", "--datadim", "2.5d", "--slice", "tx", "--imgchannel", "5", "--epochs", "3", "--gpu", "0", "--avo_theta"]
+                        + [str(t) for t in THETA])
+    T = Interpolator(a, str(tmp_path))
+    T.load_data({"image": np.zeros((8, 8, 5)), "mask": np.ones((8, 8, 5)), "name": "0"})
+    T.out_best, T.elapsed = T.img * T.mask, 0.0            # what main() does for a flat patch
+    T.save_result()
+    run = np.load(tmp_path / "0_run.npy", allow_pickle=True).item()
+    assert run["avo_model"] is None and run["avo_theta"] == THETA
+
+
+def test_without_the_flag_nothing_changes(golden, tmp_path):
+    """The 2.5-D trajectory fixture of tests/test_gpu_nets.py, eager, with its tolerances: the hook in net_forward is inert, the network
+    keeps the patch's channel count and the result file has no new field."""
+    from deep_prior_interpolation_amd.main import Interpolator
+    g = golden("net_mulresunet25d_tiny")
+    a = Namespace(**jstr(g["args"]))
+    K = len(g["loss"])
+    a.epochs, a.gpu = K, 0
+    T = Interpolator(a, str(tmp_path))
+    T.load_data({"image": g["image"], "mask": g["mask"], "name": "0"})
+    T.build_model()
+    assert T.avo is None and T.net_outchannel() == 3 == g["image"].shape[-1]
+    T.net.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in g["init_state"].items()})
+    T.net.to(DEV)
+    T.input_ = torch.from_numpy(np.array(g["z"], dtype=np.float32)).to(DEV)
+    T.optimize(net_inputs=[torch.from_numpy(np.array(x, dtype=np.float32)).to(DEV) for x in g["net_inputs"]], verbose=False, mode="eager")
+    np.testing.assert_allclose(T.history.loss, g["loss"], rtol=5e-3)
+    np.testing.assert_allclose(T.history.snr, g["snr"], atol=0.1)
+    np.testing.assert_allclose(T.history.pcorr, g["pcorr"], atol=1e-2)
+    assert np.argmin(T.history.loss) == np.argmin(g["loss"])
+    ref = np.asarray(g["out_best"], np.float64)
+    assert T.out_best.shape == ref.shape and np.linalg.norm(T.out_best - ref) < 1e-2 * np.linalg.norm(ref)
+    assert T._avo_op is None
+    T.save_result()
+    run = np.load(tmp_path / "0_run.npy", allow_pickle=True).item()
+    assert not any(k.startswith("avo") for k in run)
