@@ -797,6 +797,9 @@ __global__ __launch_bounds__(256) void lrelu_bwd_kernel(const float* __restrict_
 __device__ __forceinline__ float act_fwd_one(int kind, float x) {
   if (kind == DPI_ACT_ELU) return x > 0.f ? x : expm1f(x);
   if (kind == DPI_ACT_TANH) return tanhf(x);
+  // below -87 the sum 1 + e^-x is e^-x in fp32, and e^-x overflows from 88.73 on: 1 / (1 + inf) returned 0 where sigmoid(x) = e^x is
+  // still a (subnormal) float.  Above -87 the expression is unchanged.
+  if (x < -87.f) return expf(x);
   return 1.f / (1.f + expf(-x));
 }
 __device__ __forceinline__ float act_bwd_one(int kind, float y, float dy) {

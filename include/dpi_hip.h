@@ -170,6 +170,16 @@ int dpi_conv_bwd_weight(const dpi_conv_desc* d, const float* x, const float* x_c
 /* ---------------------------------------------------------------- BatchNorm / activations -------
  * Replaces nn.BatchNorm3d/2d in training mode (base.py:164,214; mulresunet.py:80-81,104,225) and
  * LeakyReLU(0.2) (base.py:102), plus their backward.
+ *
+ * Precondition of every entry point of this section and of the element-wise ones further down (dpi_chain_add_*, dpi_join_bwd, the *_io
+ * twins, dpi_add, dpi_lrelu_bwd, dpi_act_*, dpi_axpy): the float4 / packed-bf16 paths are chosen from V % 4 (n % 4) ALONE, the base
+ * addresses are not consulted (unlike the convolution files, which ask dpi_vec4_base).  A tensor with V % 4 == 0 must therefore be
+ * 16-byte aligned (8-byte for a bf16 tensor) — what a channel slice of a 16-byte-aligned allocation is; an element-aligned base is served
+ * only with V % 4 != 0, where the element-wise path runs.  A base that is off 16 bytes while V % 4 == 0 is neither served nor refused.
+ * dpi_upsample2x_fwd_io with a bf16 y stores pairs of outputs as one dword where the element offset into y is even: y itself must then
+ * be 4-byte aligned.  tests/test_gpu_elementwise_contract.py launches inside this precondition only, and asserts it of its buffers.
+ * The streaming reductions cut a channel into dpi_stat_blocks(C, V) = min(ceil(V / 16384), 2048) spans of ceil(V / nblk) voxels rounded
+ * up to a multiple of 4; every one of the nblk partial rows is written.
  */
 int dpi_stat_blocks(int C, size_t V);
 /* partials[nblk][C][2] of T(x) over the V voxels of each channel */

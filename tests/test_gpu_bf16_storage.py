@@ -404,7 +404,7 @@ def test_chain_apply_add_stats_and_channel_stats_bf16(ops, C_, shape):
     np.testing.assert_allclose(got[:, 1].cpu().numpy(), (act * act).sum(1).cpu().numpy(), rtol=1e-6)
 
 
-@pytest.mark.parametrize("C_,shape", [(6, (6, 8, 12)), (3, (5, 7, 9)), (25, (8, 16, 32))])
+@pytest.mark.parametrize("C_,shape", [(6, (6, 8, 12)), (3, (5, 7, 9)), (25, (8, 16, 32)), (6, (4, 17, 241)), (6, (5, 29, 113))])      # the last two: two reduction blocks
 def test_batchnorm_backward_kernels_bf16(ops, C_, shape):
     """reduce / apply / apply_fork / apply_dual with bf16 forward tensors and bf16 gradients: same partials, dx == round(fp32 dx), and the
     follow-up partials a fork / dual emits describe the STORED (rounded) dx."""
@@ -516,7 +516,8 @@ def _net_run(shape, precision, epochs, seed=3, inputdepth=16, extra=()):
     return T
 
 
-@pytest.mark.parametrize("C,shape,fork", [(25, (8, 16, 32), (12, 25)), (16, (6, 10, 12), None), (6, (5, 7, 9), (4, 6))])
+@pytest.mark.parametrize("C,shape,fork", [(25, (8, 16, 32), (12, 25)), (16, (6, 10, 12), None), (6, (5, 7, 9), (4, 6)),
+                                          (6, (4, 17, 241), (4, 6)), (6, (5, 29, 113), None)])      # V = 16388, 16385: two reduction blocks
 def test_join_kernels_with_bf16_tensors_equal_the_rounded_fp32_call(ops, C, shape, fork):
     """Round 5: dpi_join_bwd / dpi_chain_add_apply / dpi_chain_add_stats(t = NULL) with bf16 tensors: a bf16 element is widened exactly on load,
     arithmetic and the nested per-channel sums are fp32 / double, results are rounded to nearest-even on store — so every stored tensor must be

@@ -349,7 +349,8 @@ def test_bn_large_offset(ops):
 
 
 @pytest.mark.parametrize("C,shape,fork,chain_b", [(25, (12, 16, 24), (12, 25), True), (16, (9, 11, 13), None, False), (6, (16, 16, 32), (4, 6), True),
-                                                   (51, (8, 8, 16), (25, 51), True), (13, (5, 7, 9), None, False)])
+                                                   (51, (8, 8, 16), (25, 51), True), (13, (5, 7, 9), None, False),
+                                                   (6, (4, 17, 241), (4, 6), True), (6, (5, 29, 113), None, False)])      # V = 16388, 16385: two reduction blocks
 def test_join_bwd_two_pass_vs_float64_autograd_and_the_four_kernel_sequence(ops, C, shape, fork, chain_b):
     """dpi_join_bwd (ABI 403, round 5): the BatchNorm backward of a residual join — y = BN(act(t)), t = act(BN_a(xa)) + BN_b(T_b(xb)) with, on
     the fork range, one more BatchNorm under T_b (Block3d, reference mulresunet.py:85-96), or t = act(BN_a(xa)) + act(BN_b(xb)) (ResPath3d,
