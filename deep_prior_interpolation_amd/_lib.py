@@ -127,6 +127,10 @@ SIGNATURES = {
     # library fails on the unresolved symbols
     "dpi_avo_fwd": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
     "dpi_avo_adj": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
+    # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
+    # stale library fails on the unresolved symbols
+    "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "dpi_trace_sample_adj": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "dpi_max_ws_floats": (_Z, [_Z]),
     "dpi_scaled_max": (_I, [_P, _Z, _F, _P, _P, _P]),
     "dpi_threshold": (_I, [_P, _Z, _P, _P, _P]),

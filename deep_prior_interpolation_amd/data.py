@@ -15,7 +15,7 @@ import numpy as np
 
 from . import utils as u
 
-__all__ = ["extract_patches", "reconstruct_patches", "patch_extractor_for", "transpose_patches_25d"]
+__all__ = ["extract_patches", "load_trace_offsets", "reconstruct_patches", "patch_extractor_for", "transpose_patches_25d"]
 
 
 def patch_extractor_for(in_shape, patch_shape, patch_stride, datadim, imgchannel=None) -> u.PatchExtractor:
@@ -54,13 +54,15 @@ _transpose_patches_25d = transpose_patches_25d
 
 
 def extract_patches(args) -> List[dict]:
-    """List of {'image': patch*gain, 'mask': binary patch, 'name': zero-padded index} (data.py:44-84)."""
+    """List of {'image': patch*gain, 'mask': binary patch, 'name': zero-padded index} (data.py:44-84).  With --trace_offsets (ours) each
+    dict gains 'offsets', the (X, Y, 2) window of the file (2-D: (X, 1, 2) with dy = 0) cut at the origin of its image and mask windows."""
     original = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     corrupted = np.load(os.path.join(args.imgdir, args.maskname), allow_pickle=True)
     assert original.shape == corrupted.shape, "Original and Corrupted data must have the same dimension"
     assert original.ndim in [2, 3], "Data volumes have to be 2D or 3D"
     if np.isnan(corrupted).any():
         corrupted = u.bool2bin(corrupted)
+    off = load_trace_offsets(args, original.shape)       # --trace_offsets: refused here, before any window is cut, where it cannot be served
     pe = patch_extractor_for(original.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
     if args.datadim == "2.5d" or (args.datadim == "2d" and pe.ndim == 3):
         final_shape = (-1,) + pe.dim              # last axis = channels
@@ -76,6 +78,7 @@ def extract_patches(args) -> List[dict]:
     if args.datadim == "2.5d":
         img = transpose_patches_25d(img, args.slice)
         msk = transpose_patches_25d(msk, args.slice)
+    offs = _trace_offset_windows(args, off, original.shape, pe)
     width = u.ten_digit(img.shape[0])
     out = []
     for p in range(img.shape[0]):
@@ -83,7 +86,52 @@ def extract_patches(args) -> List[dict]:
         if args.adirandel > 0:
             m = u.add_rand_mask(m, args.adirandel)
         out.append({"image": img[p] * args.gain, "mask": m, "name": str(p).zfill(width)})
+        if offs is not None:
+            out[-1]["offsets"] = offs[p]
     return out
+
+
+def load_trace_offsets(args, vol_shape):
+    """--trace_offsets: the file as (X, Y, 2) fp32 for a (T, X, Y) volume, (X, 1, 2) with dy = 0 for a (T, X) section; None when the flag is
+    off.  A geometry the flag does not serve, a wrong shape, non-finite values and |d| > 0.5 raise ValueError."""
+    name = getattr(args, "trace_offsets", None)
+    if name is None:
+        return None
+    if args.datadim == "2d" and len(vol_shape) == 3:
+        raise ValueError("--trace_offsets with --datadim 2d needs a (T, X) section: %s is a 3-D volume whose last axis becomes channels, "
+                         "across which nothing can be sampled" % (args.imgname,))
+    if args.datadim not in ("2d", "3d") or len(vol_shape) != (2 if args.datadim == "2d" else 3):
+        raise ValueError("--trace_offsets needs --datadim 3d on a (T, X, Y) volume or --datadim 2d on a (T, X) section, got --datadim %s on "
+                         "a volume of shape %s" % (args.datadim, tuple(vol_shape)))
+    off = np.load(os.path.join(args.imgdir, name), allow_pickle=False)
+    if len(vol_shape) == 2:
+        want = "(%d,) or (%d, 1)" % (vol_shape[1], vol_shape[1])
+        ok = off.shape in ((vol_shape[1],), (vol_shape[1], 1))
+    else:
+        want = "(%d, %d, 2)" % (vol_shape[1], vol_shape[2])
+        ok = off.shape == (vol_shape[1], vol_shape[2], 2)
+    if not ok or off.dtype.kind not in "fiu":
+        raise ValueError("--trace_offsets %s holds %s %s for a volume of shape %s: expected real numbers of shape %s"
+                         % (name, off.dtype, tuple(off.shape), tuple(vol_shape), want))
+    off = off.astype(np.float32)
+    if len(vol_shape) == 2:
+        off = np.stack([off.reshape(-1, 1), np.zeros((off.size, 1), dtype=np.float32)], axis=-1)
+    if not np.all(np.isfinite(off)):
+        raise ValueError("--trace_offsets %s holds non-finite values" % name)
+    if np.abs(off).max() > 0.5:
+        raise ValueError("--trace_offsets %s: offsets are in grid cells and must lie in [-0.5, 0.5] (a trace belongs to the bin it is "
+                         "nearest to), got |d| up to %g" % (name, float(np.abs(off).max())))
+    return off
+
+
+def _trace_offset_windows(args, off, vol_shape, pe):
+    """The offset windows (num_patches, X, Y, 2) in the order of the image windows: the (x, y) part of the same origins, crop or cover."""
+    if off is None:
+        return None
+    origins = u.window_origins(vol_shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
+    if len(vol_shape) == 2:
+        return np.stack([off[int(o[1]):int(o[1]) + int(pe.dim[1])] for o in origins])
+    return np.stack([off[int(o[1]):int(o[1]) + int(pe.dim[1]), int(o[2]):int(o[2]) + int(pe.dim[2])] for o in origins])
 
 
 def _reconstruct_avo_model(args, results_root):

@@ -16,7 +16,7 @@ from . import utils as u
 from .architectures import build_net
 from .data import extract_patches
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import check_avo, check_out_ema, net_args_are_same, parse_arguments
+from .parameter import check_avo, check_out_ema, check_trace_offsets_flag, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -48,6 +48,10 @@ class Interpolator:
         # --avo_theta (ours): the net outputs three elastic-parameter sections, the AVO operator maps them to the angle sections (net_forward)
         self.avo = check_avo(args)                               # None, or (theta, vsvp, linearization)
         self._avo_op = None                                      # built per patch length T (net_forward)
+        # --trace_offsets (ours): the loss sees the grid output sampled at the recorded trace positions (data_forward)
+        self.trace_offsets_file = check_trace_offsets_flag(args)
+        self.trace_offsets = None                                # per patch: (X, Y, 2) as used, i.e. zero at unknown traces
+        self._sampling_op = None                                 # per patch: TraceSampling, its offsets on the device (load_data)
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
         self.optimizer_kind = getattr(args, "optimizer", "adam")
         if self.optimizer_kind not in ("adam", "sgld", "psgld"):
@@ -100,7 +104,40 @@ class Interpolator:
         self.img_ = to_dev(self.img)
         self.mask_ = to_dev(self.mask)
         self.holdout_sel = self._holdout_dev = None
+        self._load_trace_offsets(data.get("offsets"))
         return torch.std(self.img_ * self.mask_).item()
+
+    def _load_trace_offsets(self, offsets):
+        """--trace_offsets: the patch's (X, Y, 2) offsets -> the sampling operator behind the network's output (data_forward).  Offsets of
+        traces the mask marks unknown are zeroed: the operator is the identity there, so nothing off-grid leaks into a trace no data
+        belongs to.  The offsets go to the device here, before iteration 0: a captured iteration replays the operator unchanged."""
+        self.trace_offsets = self._sampling_op = None
+        if self.trace_offsets_file is None:
+            if offsets is not None:
+                raise ValueError("patch %s carries trace offsets but --trace_offsets is off" % (self.image_name,))
+            return
+        if offsets is None:
+            raise ValueError("--trace_offsets %s: patch %s carries no offsets (data.extract_patches cuts them)"
+                             % (self.trace_offsets_file, self.image_name))
+        off = np.asarray(offsets, dtype=np.float32)
+        if self.img.ndim not in (3, 4) or off.shape != (self.img.shape[1], self.img.shape[2] if self.img.ndim == 4 else 1, 2):
+            raise ValueError("--trace_offsets: offsets %s do not belong to a patch of shape %s: expected (X, Y, 2)"
+                             % (tuple(off.shape), tuple(self.img.shape)))
+        known = (np.asarray(self.mask) != 0).any(axis=(0, -1)).reshape(off.shape[:2])
+        self.trace_offsets = off * known[..., None].astype(np.float32)
+        from .operators import TraceSampling
+        try:
+            self._sampling_op = TraceSampling(np.moveaxis(self.trace_offsets, -1, 0))       # [2][X][Y]
+        except ValueError as e:
+            raise ValueError("--trace_offsets: %s" % e) from e
+        self._sampling_op.upload(self.device)
+
+    def data_forward(self, out_):
+        """What the loss compares with the recorded traces: the grid output itself, or with --trace_offsets the grid output sampled at the
+        recorded trace positions.  Everything that keeps an output (out_best, --save_every, the --aa_weight term) keeps the grid tensor."""
+        if self._sampling_op is None:
+            return out_
+        return self._sampling_op(out_)                           # fp32 in every --precision mode: the output layer writes fp32
 
     def build_holdout(self):
         """--holdout: draw the per-trace split of the loaded patch from the patch seed (begin_patch) and upload it once.  optimize() and
@@ -481,10 +518,11 @@ class Interpolator:
         if self.is_sampler():
             self._moments_update(out_)
         ema = self._ema_pass(out_) if self.out_ema > 0.0 else None
+        data_ = self.data_forward(out_)                          # --trace_offsets: the misfit is measured where the traces were recorded
         if self._holdout_dev is None:
-            total_loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, self.loss_kind)
+            total_loss, metrics = ops.masked_loss(data_, self.img_, self.mask_, self.loss_kind)
         else:
-            total_loss, metrics = ops.masked_loss_holdout(out_, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
+            total_loss, metrics = ops.masked_loss_holdout(data_, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
         reg = self.regularization(out_, total_loss)          # None, or (weight tensor / float, reg loss) of a subclass / add-on
         if reg is None:
             total_loss.backward()
@@ -697,10 +735,11 @@ class Interpolator:
             if self.is_sampler():
                 self._moments_update(out_)
             ema = self._ema_pass(out_) if ema_on else None
+            data_ = self.data_forward(out_)
             if ho is None:
-                loss, metrics = ops.masked_loss(out_, self.img_, self.mask_, kind)
+                loss, metrics = ops.masked_loss(data_, self.img_, self.mask_, kind)
             else:
-                loss, metrics = ops.masked_loss_holdout(out_, self.img_, self.mask_, ho, kind)
+                loss, metrics = ops.masked_loss_holdout(data_, self.img_, self.mask_, ho, kind)
             loss.backward()
             ops.finish_backward(self._grad_params())
             opt.step()                                   # skipped on the device once `active` is 0
@@ -815,6 +854,8 @@ class Interpolator:
             run["best_iter"] = self.best_iter
         if self.avo is not None:
             run.update(avo_theta=list(self.avo[0]), avo_vsvp=self.avo[1], avo_linearization=self.avo[2], avo_model=self.avo_model())
+        if self.trace_offsets_file is not None:
+            run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)

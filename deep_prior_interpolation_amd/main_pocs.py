@@ -37,6 +37,9 @@ class Interpolator(_Base):
         if getattr(args, "avo_theta", None) is not None:
             raise ValueError("main_pocs does not support --avo_theta: the POCS projection thresholds the spectrum of a section, which knows "
                              "nothing of the three-parameter subspace the AVO operator confines the output to; run main.py")
+        if getattr(args, "trace_offsets", None) is not None:
+            raise ValueError("main_pocs does not support --trace_offsets: the POCS projection re-inserts the traces at their grid nodes, "
+                             "which is the assumption the flag removes; run main.py")
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

@@ -1,0 +1,70 @@
+"""Sampling of a regular-grid tensor at the recorded trace positions (ours, --trace_offsets: the reference takes every known trace to
+sit on a grid node).  forward / adjoint are dpi_trace_sample_fwd / dpi_trace_sample_adj (include/dpi_hip.h has the definition): bilinear
+in (x, y) from the per-trace offsets, the same for every t and every channel, edges clamped, the adjoint a deterministic gather."""
+import numpy as np
+import torch
+
+from .. import _lib
+from .base import LinearOpFn
+
+__all__ = ["TraceSampling", "check_trace_offsets"]
+
+
+def check_trace_offsets(offsets, what="offsets"):
+    """offsets (2, X, Y) -> contiguous fp32 numpy array; ValueError for another shape, non-finite values and |d| > 0.5."""
+    off = np.asarray(offsets.detach().cpu().numpy() if torch.is_tensor(offsets) else offsets)
+    if off.ndim != 3 or off.shape[0] != 2 or off.shape[1] < 1 or off.shape[2] < 1:
+        raise ValueError("%s must have the shape (2, X, Y) (plane 0 dx, plane 1 dy), got %s" % (what, tuple(off.shape)))
+    off = np.ascontiguousarray(off, dtype=np.float32)
+    if not np.all(np.isfinite(off)):
+        raise ValueError("%s hold non-finite values" % what)
+    if np.abs(off).max() > 0.5:
+        raise ValueError("%s must lie in [-0.5, 0.5] grid cells (a trace belongs to the bin it is nearest to), got |d| up to %g"
+                         % (what, float(np.abs(off).max())))
+    return off
+
+
+class TraceSampling(torch.nn.Module):
+    """forward: (1, C, T, X[, Y]) on the grid -> the same shape at the trace positions; adjoint: its exact transpose.  `offsets` is
+    (2, X, Y) — dx, dy per trace in grid cells, |d| <= 0.5 — as numpy array or tensor; a 4-D tensor (1, C, T, X) is the case Y = 1.  The
+    offsets are checked here and uploaded once per device.  A tensor whose (X, Y) differs from the offsets and a batch other than 1 raise
+    ValueError before any launch."""
+
+    def __init__(self, offsets):
+        super().__init__()
+        self._off32 = check_trace_offsets(offsets)
+        self.X, self.Y = int(self._off32.shape[1]), int(self._off32.shape[2])
+        self.offsets = torch.from_numpy(self._off32)
+        self._dev = {}
+
+    def upload(self, device):
+        """The offsets on `device`, uploaded at the first call for it (call it ahead of a graph capture, or run one eager iteration)."""
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = self.offsets.to(device)
+        return self._dev[key]
+
+    def _apply(self, x, adjoint):
+        if x.ndim not in (4, 5):
+            raise ValueError("TraceSampling works on (1, C, T, X[, Y]) tensors, got %d axes" % x.ndim)
+        if x.shape[0] != 1:
+            raise ValueError("TraceSampling works on one patch at a time: batch size %d" % x.shape[0])
+        grid = (int(x.shape[3]), int(x.shape[4]) if x.ndim == 5 else 1)
+        if grid != (self.X, self.Y):
+            raise ValueError("TraceSampling built from offsets of a %d x %d (X, Y) grid got a tensor of %d x %d"
+                             % (self.X, self.Y, grid[0], grid[1]))
+        C_, T_ = int(x.shape[1]), int(x.shape[2])
+        if C_ < 1 or T_ < 1:
+            raise ValueError("TraceSampling: empty tensor %s" % (tuple(x.shape),))
+        off = self.upload(x.device)
+        y = torch.empty_like(x)
+        L = _lib.load()
+        fn, name = (L.dpi_trace_sample_adj, "dpi_trace_sample_adj") if adjoint else (L.dpi_trace_sample_fwd, "dpi_trace_sample_fwd")
+        _lib.check(fn(_lib.ptr(x), _lib.ptr(off), C_, T_, self.X, self.Y, _lib.ptr(y), _lib.stream()), name)
+        return y
+
+    def forward(self, x):
+        return LinearOpFn.apply(x, self, False)
+
+    def adjoint(self, y):
+        return LinearOpFn.apply(y, self, True)

@@ -559,7 +559,7 @@ def main(argv=None):
         u.write_args(os.path.join(outpath, "args.txt"), args)
     if world > 1:
         dist.barrier()
-    patches = extract_patches(args)
+    patches = extract_patches(args)          # with --trace_offsets each dict carries its "offsets" window to load_data; re-assembly blends grid outputs
     vol = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     pe = patch_extractor_for(vol.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
     origins = u.window_origins(vol.shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])

@@ -129,6 +129,12 @@ _FLAGS = [
     (("--avo_vsvp",), dict(type=float, required=False, default=0.5, help="ours: vs/vp ratio of the AVO coefficients (--avo_theta)")),
     (("--avo_linearization",), dict(type=str, required=False, default="akirich", choices=["akirich", "fatti"],
                                    help="ours: Aki-Richards or Fatti form of the AVO coefficients (--avo_theta)")),
+    # off-grid traces (ours: the reference takes every known trace to sit on a grid node)
+    (("--trace_offsets",), dict(type=str, required=False,
+                               help="ours: a .npy in --imgdir with the recorded position of every trace minus its bin centre, in grid cells "
+                                    "(|d| <= 0.5; absent = off): (X, Y, 2) = dx, dy for --datadim 3d on a (T, X, Y) volume, (X,) or (X, 1) = dx "
+                                    "for --datadim 2d on a (T, X) section.  The loss then compares the traces with the network's grid output "
+                                    "sampled bilinearly at those positions; what is selected and saved stays the regular-grid output")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -163,8 +169,29 @@ def postprocess(args: Namespace) -> Namespace:
         raise ValueError("--holdout must lie in [0, 0.5], got %r" % args.holdout)
     _postprocess_sampler(args)
     check_out_ema(args)
+    check_trace_offsets_flag(args)
     check_avo(args)
     return args
+
+
+def check_trace_offsets_flag(args: Namespace):
+    """--trace_offsets and what it cannot be combined with; returns the file name, or None when it is off (also for a Namespace without the
+    key, as those of older args.txt files).  The file itself is read and checked by data.extract_patches."""
+    name = getattr(args, "trace_offsets", None)
+    if name is None:
+        return None
+    if getattr(args, "avo_theta", None) is not None:
+        raise ValueError("--trace_offsets does not combine with --avo_theta, which needs --datadim 2.5d")
+    if args.datadim not in ("2d", "3d"):
+        raise ValueError("--trace_offsets needs --datadim 2d or 3d, got --datadim %s: a 2.5-D slab stacks one spatial axis into channels, "
+                         "across which nothing can be sampled" % args.datadim)
+    if (getattr(args, "out_ema", 0.0) or 0.0) != 0.0:
+        raise ValueError("--trace_offsets does not combine with --out_ema (got %g): the misfit of the running average is evaluated inside "
+                         "a fused kernel that compares grid node with trace sample by sample" % args.out_ema)
+    if getattr(args, "optimizer", "adam") != "adam":
+        raise ValueError("--trace_offsets does not combine with --optimizer %s: the misfit of the posterior mean is evaluated on the grid, "
+                         "not at the recorded positions" % args.optimizer)
+    return name
 
 
 def check_avo(args: Namespace):
@@ -254,6 +281,9 @@ def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
     ta, tb = a.get("avo_theta"), b.get("avo_theta")
     if (None if ta is None else [float(t) for t in ta]) != (None if tb is None else [float(t) for t in tb]):
         errors.append("avo_theta")
+    # --trace_offsets (ours) decides what the weights were fitted to; args.txt files of older runs lack the key: off
+    if a.get("trace_offsets") != b.get("trace_offsets"):
+        errors.append("trace_offsets")
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

@@ -15,7 +15,8 @@ down to a quarter), so that (128, 64, 64) or (48, 32, 32) stand-ins hold as many
 bench patch): kept because committed reference recordings (`tests/golden/plateau_96x64x64.npz`) were made on it."""
 import numpy as np
 
-__all__ = ["hyperbolic_volume", "tiled_hyperbolic_volume", "sparse_hyperbolic_volume", "random_trace_mask", "coarse_std", "avo_gathers"]
+__all__ = ["hyperbolic_volume", "tiled_hyperbolic_volume", "sparse_hyperbolic_volume", "random_trace_mask", "coarse_std", "avo_gathers",
+           "hyperbolic_traces"]
 
 TARGET_RMS = 0.19          # std of the un-gained cube: 40 * 0.19 * sqrt(0.34) = 4.4, the middle of the notebook's 3.94 .. 5.16
 
@@ -104,6 +105,37 @@ def avo_gathers(shape, theta, vsvp=0.5, seed=0, linearization="akirich", return_
     G = avo_coefficients(theta, vsvp, 1, linearization)[:, :, 0]                  # (ntheta, 3)
     data = np.einsum("ak,txk->txa", G, model).astype(dtype)
     return (data, model) if return_model else data
+
+
+def hyperbolic_traces(shape, offsets, seed=0, dtype=np.float32):
+    """Stand-in for irregular acquisition (--trace_offsets): the events of `hyperbolic_volume(shape, seed, background=0)` evaluated
+    analytically at the recorded positions (x + dx, y + dy) instead of the bin centres.  `offsets` is (X, Y, 2) in grid cells, the layout of
+    the flag's file.  The generator is consumed exactly as `hyperbolic_volume` consumes it and the amplitude scale is that of the on-grid
+    cube, so both are the same wavefield: at zero offsets the result equals `hyperbolic_volume(shape, seed, background=0)` bit for bit."""
+    rng = np.random.RandomState(seed)
+    nt, nx, ny = shape
+    off = np.asarray(offsets, dtype=np.float32)
+    if off.shape != (nx, ny, 2):
+        raise ValueError("offsets must have the shape (X, Y, 2) = %r, got %r" % ((nx, ny, 2), tuple(off.shape)))
+    s = min(1.0, max(0.25, nt / 256.0))
+    f0 = 0.055 / s
+    t = np.arange(nt, dtype=np.float32)[:, None, None]
+    gx, gy = np.arange(nx, dtype=np.float32)[None, :, None], np.arange(ny, dtype=np.float32)[None, None, :]
+    r2_grid = (gx / max(nx, 1)) ** 2 + (gy / max(ny, 1)) ** 2
+    r2_rec = ((gx + off[None, :, :, 0]) / max(nx, 1)) ** 2 + ((gy + off[None, :, :, 1]) / max(ny, 1)) ** 2
+    grid = np.zeros(shape, dtype=np.float32)
+    rec = np.zeros(shape, dtype=np.float32)
+    t0 = rng.uniform(0.12, 0.22) * nt
+    while t0 < 1.05 * nt:
+        c = 0.9 - 0.3 * min(t0 / nt, 1.0) + rng.uniform(-0.04, 0.04)
+        amp = rng.uniform(0.5, 1.0) * rng.choice([-1.0, 1.0])
+        for vol, r2 in ((grid, r2_grid), (rec, r2_rec)):
+            tt = np.sqrt(t0 ** 2 + r2 * (nt * c) ** 2)
+            a = (np.pi * f0 * (t - tt)) ** 2
+            vol += (amp * (1.0 - 2.0 * a) * np.exp(-a)).astype(np.float32)
+        t0 += rng.uniform(18.0, 32.0) * s
+    rec *= TARGET_RMS / max(float(grid.std()), 1e-12)
+    return rec.astype(dtype)
 
 
 def random_trace_mask(shape, rate, seed=0, dtype=np.float32):

@@ -550,6 +550,22 @@ int dpi_structure_tensor_sections(const float* x, int C, int T, int X, int Y, fl
 int dpi_avo_fwd(const float* x, const float* G, int ntheta, int T, size_t S, float* y, void* stream);
 int dpi_avo_adj(const float* y, const float* G, int ntheta, int T, size_t S, float* x, void* stream);
 
+/* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
+ * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
+ * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]
+ * fp32, plane 0 dx, plane 1 dy: the recorded position minus the bin centre in units of the grid spacing, |d| <= 0.5.  Per axis, from d
+ * alone (no x + d in floating point): d >= 0 -> taps i and i + 1 with weights 1 - d and d; d < 0 -> taps i - 1 and i with weights -d and
+ * 1 + d.  Tap indices are clamped to [0, n - 1] (nearest-edge extrapolation); two taps that clamp onto the same node both count, so the
+ * weights of a trace always sum to 1.
+ *     dpi_trace_sample_fwd:  y[c][t][x][y] = sum over the 2 x 2 taps of wx * wy * in[c][t][tap_x][tap_y]
+ *     dpi_trace_sample_adj:  the exact transpose as a gather: grid node (x', y') collects from the 3 x 3 traces around it the weights of
+ *                            their clamped taps that are (x', y').  No atomics, sums in a fixed order: deterministic.
+ * Zero offsets make both the identity bit for bit.  The tap indices never depend on the size of d, so offsets out of range or not finite
+ * cannot address out of bounds (the Python operator refuses them).  Null pointers, in == out, a non-positive size and more than 2^60
+ * elements return an error before any launch.  ABI version stays: a stale library fails on the unresolved symbols. */
+int dpi_trace_sample_fwd(const float* x, const float* off, int C, int T, int X, int Y, float* y, void* stream);
+int dpi_trace_sample_adj(const float* y, const float* off, int C, int T, int X, int Y, float* x, void* stream);
+
 /* ---------------------------------------------------------------- POCS regulariser --------------
  * Replaces utils/pocs.py:5-19 (threshold / compute_threshold: out = max(x) * scale with scale = perc/100, kept on the device;
  * y = x * ((x > th) + (x < -th)) on the real view of the spectrum) and :80-84 (y = weighted_data + weighted_mask * x).
