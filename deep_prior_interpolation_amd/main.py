@@ -472,7 +472,7 @@ class Interpolator:
         patches) 8.4-8.8 against 8.2 it/s — so it is on for every storage type."""
         if getattr(self.args, "net", "multiunet") == "part":
             # every `down` convolution of the partial-convolution net is used twice (on the tensor and on the hole map): autograd ACCUMULATES its
-            # weight gradient on the main stream, which a side stream that has not run yet cannot feed (ops._deferred)
+            # weight gradient on the main stream, which a side stream that has not run yet cannot feed (ops.sched.deferred)
             return False
         big = int(np.prod(self.img.shape[:-1])) >= (1 << 20)
         if os.environ.get("DPI_FORCE_OVERLAP") in ("0", "1"):       # A/B knob
@@ -514,15 +514,7 @@ class Interpolator:
             _lib.check(_lib.load().dpi_axpy(float(self.add_data_weight[self.iiter]), _lib.ptr(self.add_data_), input_.numel(),
                                             _lib.ptr(input_), _lib.stream()), "dpi_axpy")
             self.input_list.append(u.torch_to_np(input_, True))
-        out_ = self.net_forward(input_)
-        if self.is_sampler():
-            self._moments_update(out_)
-        ema = self._ema_pass(out_) if self.out_ema > 0.0 else None
-        data_ = self.data_forward(out_)                          # --trace_offsets: the misfit is measured where the traces were recorded
-        if self._holdout_dev is None:
-            total_loss, metrics = ops.masked_loss(data_, self.img_, self.mask_, self.loss_kind)
-        else:
-            total_loss, metrics = ops.masked_loss_holdout(data_, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
+        out_, ema, total_loss, metrics = self._forward_and_loss(input_)
         reg = self.regularization(out_, total_loss)          # None, or (weight tensor / float, reg loss) of a subclass / add-on
         if reg is None:
             total_loss.backward()
@@ -569,9 +561,23 @@ class Interpolator:
         self.iiter += 1
         return l
 
+    def _forward_and_loss(self, input_):
+        """The middle of an iteration, eager or captured: forward, posterior moments, running average, misfit.  Returns (out, ema metrics or
+        None, loss, metrics)."""
+        out_ = self.net_forward(input_)
+        if self.is_sampler():
+            self._moments_update(out_)
+        ema = self._ema_pass(out_) if self.out_ema > 0.0 else None
+        data_ = self.data_forward(out_)                          # --trace_offsets: the misfit is measured where the traces were recorded
+        if self._holdout_dev is None:
+            loss, metrics = ops.masked_loss(data_, self.img_, self.mask_, self.loss_kind)
+        else:
+            loss, metrics = ops.masked_loss_holdout(data_, self.img_, self.mask_, self._holdout_dev, self.loss_kind)
+        return out_, ema, loss, metrics
+
     def _grad_params(self):
         """The parameters ops.finish_backward() checks the deferred gradients against (only when a side / branch stream ran: big patches)."""
-        return self.optimizer._params if (ops._deferred and self.optimizer is not None) else None
+        return self.optimizer._params if (ops.sched.deferred and self.optimizer is not None) else None
 
     def regularization(self, out_, main_loss):
         """Extra loss term hook.  The base path has none.  With --aa_weight > 0 the anti-aliasing add-on is active:
@@ -722,7 +728,6 @@ class Interpolator:
         self._g_hist = torch.zeros(a.epochs * cols, dtype=torch.float64, device=dev)
         self._g_improved = torch.zeros(1, dtype=torch.int32, device=dev)
         self._g_best = None
-        kind = self.loss_kind
 
         def one_iteration():
             with self.precision_scope():
@@ -731,15 +736,7 @@ class Interpolator:
         def _one_iteration():
             ops.begin_iteration()
             opt.zero_grad()
-            out_ = self.net_forward(self.perturbed_input())
-            if self.is_sampler():
-                self._moments_update(out_)
-            ema = self._ema_pass(out_) if ema_on else None
-            data_ = self.data_forward(out_)
-            if ho is None:
-                loss, metrics = ops.masked_loss(data_, self.img_, self.mask_, kind)
-            else:
-                loss, metrics = ops.masked_loss_holdout(data_, self.img_, self.mask_, ho, kind)
+            out_, ema, loss, metrics = self._forward_and_loss(self.perturbed_input())
             loss.backward()
             ops.finish_backward(self._grad_params())
             opt.step()                                   # skipped on the device once `active` is 0

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check, ptr, stream
+from .schedule import Schedule
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -280,207 +281,25 @@ def raw_conv_bwd_data_dual(d3, dy3, w3, d1, dy1, w1, dx, accumulate=False):
 
 
 # ------------------------------------------------------------------------------------------------
-# side stream for weight gradients: dW of a layer depends only on (x, dy) and nothing downstream depends on it before the
-# optimiser step, so it runs concurrently with the backward-data / BatchNorm-backward chain.  At the coarse levels of the
-# U-Net a single kernel fills only part of the chip (tens to hundreds of workgroups), the pair fills more of it.
+# the stream schedule (schedule.py): side streams for weight gradients, branch streams, their joins, deferred gradients
 # ------------------------------------------------------------------------------------------------
-# Off by default: it pays when the iteration is GPU-bound (patches of >= 2^20 voxels, eager loop: 40.7 -> 39.6 ms at
-# 256x128x128) and costs host time when it is launch-bound (64^3 eager: 8.8 -> 11.3 ms).  Interpolator.optimize / bench.py
-# switch it on by patch size; DPI_OVERLAP_WGRAD=0/1 forces it.
-OVERLAP_WEIGHT_GRADS = os.environ.get("DPI_OVERLAP_WGRAD", "0") == "1"
-OVERLAP_IN_GRAPH = os.environ.get("DPI_OVERLAP_IN_GRAPH", "0") == "1"
-OVERLAP_MAX_VOXELS = int(os.environ.get("DPI_OVERLAP_MAX_VOXELS", str(1 << 40)))
-
-
-def set_weight_grad_overlap(on, in_graph=None):
-    """in_graph: keep the side stream inside a hipGraph capture too (fork / join edges in the graph).  Pays on GPU-bound patches
-    (256x128x128: 34.2 ms eager with overlap, 34.2 ms graph without, 33.8 ms graph with), costs on small ones (64^3: 7.6 vs 7.9 ms)."""
-    global OVERLAP_WEIGHT_GRADS, OVERLAP_IN_GRAPH
-    if "DPI_OVERLAP_WGRAD" not in os.environ:
-        OVERLAP_WEIGHT_GRADS = bool(on)
-    if in_graph is not None and "DPI_OVERLAP_IN_GRAPH" not in os.environ:
-        OVERLAP_IN_GRAPH = bool(in_graph)
-_side_streams = {}
-N_SIDE_STREAMS = int(os.environ.get("DPI_SIDE_STREAMS", "2"))     # weight gradients round-robin over this many side streams (four alternating bench runs each: 32.43 / 32.12 / 32.33 ms with 1 / 2 / 3)
-_side_rr = [0]
-_side_used = set()
-# Where the main stream waits for the weight-gradient streams.  "node": at the end of every fused node's backward (rounds 1-4).
-# "step": once, after the whole backward (finish_backward(), before the optimiser step): the main chain never stalls behind a
-# weight-gradient kernel, the side streams drain their backlog under the BatchNorm-backward / up-sampling passes of the nodes that
-# follow.  The tensors a side-stream launch reads or writes were allocated on the main stream's pool; they are kept referenced in
-# _side_keep until the join so that the caching allocator cannot hand their memory to a later main-stream tensor.
-# Only between begin_iteration() and finish_backward() (the Interpolator's loops); a bare loss.backward() joins per node.
-JOIN_AT = os.environ.get("DPI_JOIN_AT", "step")
-_side_keep = []
-_in_iteration = [False]
-# Gradients handed back to autograd BEFORE the stream that writes them has run (weight gradients on the side streams; with the branch stream also the
-# ResPath's BatchNorm gradients).  That is only sound if autograd's AccumulateGrad ADOPTS the tensor as .grad — which needs .grad to be None (zero_grad with
-# set_to_none=True), no hook, no second use of the parameter; anything else makes it clone or add on the main stream, ahead of the producer (ADVICE round 5).
-# finish_backward(params) checks exactly that: every deferred tensor must BE some parameter's .grad storage afterwards.
-_deferred = []
-
-
-def begin_iteration():
-    """Top of every iteration (eager or captured): the weight-gradient launches are dealt to the side streams from stream 0 again, so
-    the kernel-to-stream assignment is the same in every iteration and every run."""
-    _side_rr[0] = 0
-    _in_iteration[0] = True
-    del _deferred[:]
-
-
-def abort_iteration():
-    """An iteration raised between begin_iteration() and finish_backward(): join every stream and forget the per-iteration state, so that a later
-    bare loss.backward() joins per node again instead of believing it is still inside an Interpolator iteration."""
-    try:
-        if torch.cuda.is_available():
-            join_weight_grads(final=True)
-            join_branch()
-    finally:
-        _in_iteration[0] = False
-        _side_used.clear()
-        del _side_keep[:]
-        del _deferred[:]
-        _branch_open[0] = False
-
-
-def _defer(*tensors):
-    if JOIN_AT == "step" and _in_iteration[0]:
-        _deferred.extend(t.data_ptr() for t in tensors if t is not None)
-
-
-def _side_stream():
-    dev = torch.cuda.current_device()
-    sts = _side_streams.get(dev)
-    if sts is None:
-        sts = [torch.cuda.Stream(device=dev) for _ in range(max(N_SIDE_STREAMS, 1))]
-        _side_streams[dev] = sts
-    i = _side_rr[0] % len(sts)
-    _side_rr[0] += 1
-    _side_used.add(i)
-    return sts[i]
+sched = Schedule()
+set_weight_grad_overlap = sched.set_overlap
+begin_iteration = sched.begin
+abort_iteration = sched.abort
+finish_backward = sched.finish
 
 
 def conv_bwd_weight_async(d, x, chain, dy, dw):
-    """raw_conv_bwd_weight on the side stream (ordered after everything already queued on the current stream).
-    Callers must `join_weight_grads()` before returning to autograd."""
-    # (DPI_OVERLAP_MAX_VOXELS: A/B knob — restricting the side stream to the coarse levels, whose kernels leave CUs idle, measured
-    #  35.76 ms per iteration against 35.10 with every layer on it, round 3)
-    if not OVERLAP_WEIGHT_GRADS or d.D * d.H * d.W >= OVERLAP_MAX_VOXELS or (torch.cuda.is_current_stream_capturing() and not OVERLAP_IN_GRAPH):
-        # (inside a hipGraph capture the fork / join edges cost more than the overlap wins on the small patches that are
-        #  run as graphs: measured 7.6 vs 7.9 ms per iteration at 64^3)
+    """raw_conv_bwd_weight on a side stream (ordered after everything already queued on the current stream).
+    Callers must `sched.join_side()` before returning to autograd."""
+    if not sched.overlap or (torch.cuda.is_current_stream_capturing() and not sched.overlap_in_graph):
         return raw_conv_bwd_weight(d, x, chain, dy, dw)
-    side = _side_stream()
+    side = sched.side_stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         raw_conv_bwd_weight(d, x, chain, dy, dw)
-    if JOIN_AT == "step" and _in_iteration[0]:
-        # (not dw: the parameter's .grad keeps it alive until the next zero_grad, and a second reference would make autograd's
-        #  AccumulateGrad CLONE it on the main stream — before the side stream has written it — instead of adopting it)
-        _side_keep.append((x, chain, dy))
-        _deferred.append(dw.data_ptr())
-
-
-def join_weight_grads(final=False):
-    """End of a fused node's backward (final=False) / end of the whole backward (final=True, finish_backward)."""
-    if JOIN_AT == "step" and _in_iteration[0] and not final:
-        return
-    if _side_used:
-        sts = _side_streams.get(torch.cuda.current_device()) or []
-        for i in sorted(_side_used):
-            torch.cuda.current_stream().wait_stream(sts[i])
-        _side_used.clear()
-    _side_keep.clear()
-
-
-def finish_backward(params=None):
-    """After loss.backward(), before the optimiser step: every weight gradient launched on a side stream (and everything the branch
-    stream still runs) is ordered in front of whatever the current stream does next.
-    params (the optimised parameters): checks that every gradient that was handed to autograd ahead of its producer stream was ADOPTED as a
-    parameter's .grad — not cloned, not accumulated into an existing .grad (see _deferred) — and fails loudly otherwise."""
-    join_weight_grads(final=True)
-    join_branch()
-    _in_iteration[0] = False
-    if _deferred and params is not None:
-        have = {p.grad.data_ptr() for p in params if p.grad is not None}
-        lost = [q for q in _deferred if q not in have]
-        if lost:
-            n = len(_deferred)
-            del _deferred[:]
-            raise _lib.DpiError("%d of %d gradients written on a side / branch stream were copied or accumulated by autograd before that stream ran "
-                                "(zero_grad(set_to_none=False), a gradient hook, retain_grad or a shared parameter?): with the once-per-step join "
-                                "(DPI_JOIN_AT=step) .grad must be None when backward starts; use DPI_JOIN_AT=node otherwise" % (len(lost), n))
-    del _deferred[:]
-
-
-# ------------------------------------------------------------------------------------------------
-# branch stream (round 5): work that is OFF the critical path of the U-Net runs beside it instead of in front of it.
-#   forward:  the ResPath of level l (skip branch: conv3x3 + conv1x1 + join + BatchNorm, mulresunet.py:99-113) depends only on the
-#             encoder output of its level, while its consumer — the level's concat — also waits for the whole deeper U;  the 1x1x1
-#             shortcut of a MultiRes block (HBM-bound) depends only on the block input, while the three 3x3x3 layers (matrix-bound)
-#             form the chain the block output waits for.
-#   backward: the ResPath's backward (BatchNorm backward, backward-data, two weight gradients) feeds the encoder block of its level,
-#             which the deeper U's backward reaches much later.
-# An HBM-bound kernel beside a matrix-bound one costs ~20 % of its stand-alone time (tools/overlap_probe.py: 25->16 forward 0.80 ms +
-# elementwise 0.43 ms = 0.89 ms side by side), and the coarse levels' launches leave most of the chip idle.
-# Same kernels, same operands, same order per tensor: results are bit-identical to the serial schedule.
-# Memory: tensors are allocated from the launching (main) stream's pool; each one a branch-stream kernel touches is marked with
-# record_stream, so the caching allocator does not hand its memory out again before that kernel has run.
-# Only inside an Interpolator iteration with the weight-gradient overlap on (patches >= 2^20 voxels, eager loop).
-# ------------------------------------------------------------------------------------------------
-BRANCH_STREAMS = os.environ.get("DPI_BRANCH", "1") == "1"
-BRANCH_SHORTCUT = int(os.environ.get("DPI_BRANCH_SHORT", "0"))   # 0: OFF.  2 (round 6): beside the SECOND and THIRD 3x3x3 layer of the block (4->8, 8->13: matrix-bound, they read 4 / 8 channels), started once the first one has drained — measured +0.3 ms (29.7-30.1 against 29.3-29.5, profiles/r06/ab_fanin_shortcut.txt).  1: beside the first layer:     # OFF: the first 3x3x3 layer of a block (64->4, 67->4, 25->8: few output channels) is itself at ~half the HBM bandwidth, the 1x1x1 layer beside it gains nothing (64->4 0.70 -> 1.05 ms with the 0.35 ms shortcut beside it; 31.1-31.5 ms per iteration with, 30.6-30.8 without)
-BRANCH_SKIP = os.environ.get("DPI_BRANCH_SKIP", "1") == "1"
-BRANCH_SKIP_BWD = os.environ.get("DPI_BRANCH_SKIP_BWD", "1") == "1"
-_branch_streams = {}
-_branch_open = [False]
-
-
-def branch_on():
-    return (BRANCH_STREAMS and OVERLAP_WEIGHT_GRADS and _in_iteration[0] and JOIN_AT == "step"
-            and not torch.cuda.is_current_stream_capturing())
-
-
-def _branch_stream(kind="skip"):
-    key = (torch.cuda.current_device(), kind)
-    st = _branch_streams.get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=key[0])
-        _branch_streams[key] = st
-    return st
-
-
-class _Branch:
-    """with _Branch(kind, tensors...): launches go to the branch stream, ordered after everything queued on the current stream so
-    far; every tensor listed (allocated by the current stream's pool) is marked as used there."""
-
-    def __init__(self, kind, *tensors):
-        self.st = _branch_stream(kind)
-        self.tensors = tensors
-
-    def __enter__(self):
-        self.st.wait_stream(torch.cuda.current_stream())
-        for t in self.tensors:
-            if t is not None:
-                t.record_stream(self.st)
-        self.ctx = torch.cuda.stream(self.st)
-        self.ctx.__enter__()
-        _branch_open[0] = True
-        return self
-
-    def __exit__(self, *exc):
-        return self.ctx.__exit__(*exc)
-
-
-def join_branch(kind=None):
-    """The current stream waits for the branch stream(s)."""
-    if not _branch_open[0]:
-        return
-    dev = torch.cuda.current_device()
-    for (d, k), st in _branch_streams.items():
-        if d == dev and (kind is None or k == kind):
-            torch.cuda.current_stream().wait_stream(st)
-    if kind is None:
-        _branch_open[0] = False
+    sched.keep(x, chain, dy, dw)
 
 
 def raw_conv_bwd_weight(d, x, chain, dy, dw):
@@ -581,7 +400,7 @@ class ConvFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(d.Cout, dtype=torch.float32, device=x.device)
             raw_channel_sum(dy, d.Cout, dy.numel() // d.Cout, db)
-        join_weight_grads()
+        sched.join_side()
         return dx, dw, db, None
 
 
@@ -683,7 +502,6 @@ def _bn_backward_apply_dual(dy, side_a, side_b, fork=None):
 # rounds 1-4 bf16 kernels took their statistics of the ROUNDED intermediate gradient they stored; this path stores none, its sums describe
 # the fp32 values).  DPI_JOIN_BWD=0: the rounds 1-4 sequence (A/B and test knob).
 JOIN_BWD_FUSED = os.environ.get("DPI_JOIN_BWD", "1") == "1"
-EARLY_SHORTCUT_WGRAD = os.environ.get("DPI_EARLY_SHORTCUT_WGRAD", "0") == "1"     # measured: 29.47-29.57 ms with, 29.36-29.43 without (profiles/r05/ab_early_shortcut.txt): off
 
 
 def _join_backward(dy, t, mi, gamma, beta, pre_slope, side_a, side_b, fork=None, fwd_chains=None):
@@ -723,18 +541,21 @@ def _join_fused_ok(*tensors):
     return JOIN_BWD_FUSED and (all(x.dtype == torch.float32 for x in tensors) or all(x.dtype == torch.bfloat16 for x in tensors))
 
 
-def _join_forward(a, ch_a, b, ch_b, C_, V, slope, bn, gamma, beta, mi_out, y, keep_t):
+def _join_forward(a, ch_a, b, ch_b, C_, V, slope, bn, gamma, beta, mi_out, y, keep_t, t=None, ch_out=None):
     """t = T_a(a) + T_b(b);  y = bn(act(t)) written to `y` (a tensor or a channel slice of one).  Returns t, or None when it was not stored:
     with fp32 tensors and the two-pass join backward (keep_t False) the statistics pass only reads, the apply pass re-forms the sum from a
-    and b, and the backward does the same — one tensor write less forward, two tensor reads less backward, C x V floats less held."""
+    and b, and the backward does the same — one tensor write less forward, two tensor reads less backward, C x V floats less held.
+    t / ch_out: the sum and the chain of `bn` allocated by the caller (the branch path allocates on the main stream before it forks)."""
     L = _lib.load()
     dev = a.device
-    t = torch.empty_like(a) if keep_t else None
+    if keep_t and t is None:
+        t = torch.empty_like(a)
     nblk = L.dpi_stat_blocks(C_, V)
     part = torch.empty(nblk * C_ * 2, dtype=torch.float64, device=dev)
     check(L.dpi_chain_add_stats_io(ptr(a), ptr(ch_a), ptr(b), ptr(ch_b), C_, V, slope, ptr(t), ptr(part), _io(a), stream()),
           "dpi_chain_add_stats")
-    ch_out = torch.empty(C_ * 5, dtype=torch.float32, device=dev)
+    if ch_out is None:
+        ch_out = torch.empty(C_ * 5, dtype=torch.float32, device=dev)
     raw_bn_finalize(part, nblk, C_, V, gamma, beta, slope, bn.running_mean, bn.running_var, bn.num_batches_tracked, mi_out, ch_out,
                     act_first=1)
     if keep_t:
@@ -841,7 +662,7 @@ class ConvBnActFn(torch.autograd.Function):
             fan = ctx.fan
             if fan is not None and fan.dx is not None and fan.dx.shape == x.shape and fan.dx.dtype == x.dtype:
                 if fan.branched:
-                    join_branch("skip")          # the ResPath's backward-data wrote fan.dx on the branch stream
+                    sched.join_branch("skip")          # the ResPath's backward-data wrote fan.dx on the branch stream
                 raw_conv_bwd_data(d, dr, w, fan.dx, accumulate=True)
                 fan.dx = None                    # consumed: x's whole gradient now reaches autograd through the tap node (FanIn above)
             else:
@@ -849,7 +670,7 @@ class ConvBnActFn(torch.autograd.Function):
                 raw_conv_bwd_data(d, dr, w, dx)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _zeros_like_or_none(ctx.bias_ref, dr)
-        join_weight_grads()
+        sched.join_side()
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -881,6 +702,19 @@ def _zeros_like_or_none(b, dr=None):
     if DEAD_BIAS == "noise":
         return torch.randn_like(b) * 1e-6
     return dr.sum(dim=[0] + list(range(2, dr.ndim)), dtype=torch.float32)
+
+
+def _save_with_params(ctx, tensors, p):
+    """save_for_backward of a fused node: its tensors, then the parameter list `p` without the entries that are None (a conv without bias)."""
+    ctx.save_for_backward(*tensors, *[q for q in p if q is not None])
+    ctx.none_mask = [q is None for q in p]
+
+
+def _saved_with_params(ctx, n):
+    """(the n tensors, p) as _save_with_params stored them, None entries of p back in place."""
+    saved = ctx.saved_tensors
+    it = iter(saved[n:])
+    return saved[:n], [None if isnone else next(it) for isnone in ctx.none_mask]
 
 
 class Block3dFn(torch.autograd.Function):
@@ -916,10 +750,10 @@ class Block3dFn(torch.autograd.Function):
         S = torch.empty_like(R)
         chSA = torch.empty((2, Ct * 5), **f32)       # the two chains of the residual join, rows of one buffer (saved as a whole for the backward)
         chS, chA = chSA[0], chSA[1]
-        side_shortcut = BRANCH_SHORTCUT if branch_on() else 0
+        side_shortcut = sched.branch_shortcut if sched.branch_on() else 0
 
         def shortcut_on_branch():   # the 1x1x1 shortcut (HBM-bound) beside the 3x3x3 chain (matrix-bound): it only needs the block input
-            with _Branch("short", x, S, miS, chS):
+            with sched.branch("short", x, S, miS, chS):
                 _cba_raw(dsc, x, None, ws, bs, bns_, slope, S, miS, chS)
         if side_shortcut == 1:
             shortcut_on_branch()
@@ -935,7 +769,7 @@ class Block3dFn(torch.autograd.Function):
         raw_bn_stats_finalize(R, CH, Ct, V, gA, eA, 1.0, A.running_mean, A.running_var, A.num_batches_tracked, miA, chA,
                               compose=True)
         if side_shortcut:
-            join_branch("short")
+            sched.join_branch("short")
         else:
             _cba_raw(dsc, x, None, ws, bs, bns_, slope, S, miS, chS)
         # residual join + statistics of act(t) for bn2, then y = bn2(act(t))
@@ -945,8 +779,7 @@ class Block3dFn(torch.autograd.Function):
         if tless:
             t = chSA                          # what the backward re-forms t from (2 x Ct x 5 floats instead of Ct x V)
         ctx.tless = tless
-        ctx.save_for_backward(x, R, S, t, CH, mi1, mi2, mi3, miA, miS, miB, *[q for q in p if q is not None])
-        ctx.none_mask = [q is None for q in p]
+        _save_with_params(ctx, (x, R, S, t, CH, mi1, mi2, mi3, miA, miS, miB), p)
         ctx.descs = (d1, d2, d3, dsc)
         ctx.slope = float(slope)
         ctx.split = (c1, c2, c3)
@@ -955,9 +788,7 @@ class Block3dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         dy = _req(dy, "block grad", act=True)
-        x, R, S, t, CH, mi1, mi2, mi3, miA, miS, miB = ctx.saved_tensors[:11]
-        it = iter(ctx.saved_tensors[11:])
-        p = [None if isnone else next(it) for isnone in ctx.none_mask]
+        (x, R, S, t, CH, mi1, mi2, mi3, miA, miS, miB), p = _saved_with_params(ctx, 11)
         (w1, b1, g1, e1, w2, b2, g2, e2, w3, b3, g3, e3, ws, bs, gs, es, gA, eA, gB, eB) = p
         d1, d2, d3, dsc = ctx.descs
         slope = ctx.slope
@@ -981,11 +812,7 @@ class Block3dFn(torch.autograd.Function):
             del dt
             # o3 -> o2 -> o1: each conv's backward-data ACCUMULATES into the concat gradient of its input slice
             _, dg3, de3 = _bn_backward_apply(dcat[:, s3], R[:, s3], mi3, g3, e3, 1.0, slope, red3, dx=dR[:, s3])
-        # the shortcut's weight gradient (1x1x1: HBM-bound) only needs dS: issued FIRST, it runs beside the matrix-bound 3x3x3 chain below
-        # instead of beside conv1's weight gradient at the end of the node (round 5; DPI_EARLY_SHORTCUT_WGRAD=0: the old place)
         dws = torch.empty_like(ws)
-        if EARLY_SHORTCUT_WGRAD:
-            conv_bwd_weight_async(dsc, x, None, dS, dws)
         dw3 = torch.empty_like(w3)
         conv_bwd_weight_async(d3, R[:, s2], ch2, dR[:, s3], dw3)
         raw_conv_bwd_data(d3, dR[:, s3], w3, dcat[:, s2], accumulate=True)
@@ -996,13 +823,12 @@ class Block3dFn(torch.autograd.Function):
         _, dg1, de1 = _bn_backward(dcat[:, s1], R[:, s1], mi1, g1, e1, 1.0, slope, dx=dR[:, s1])
         dw1 = torch.empty_like(w1)
         conv_bwd_weight_async(d1, x, None, dR[:, s1], dw1)
-        if not EARLY_SHORTCUT_WGRAD:
-            conv_bwd_weight_async(dsc, x, None, dS, dws)
+        conv_bwd_weight_async(dsc, x, None, dS, dws)       # the shortcut's weight gradient is issued last (first was tried and lost)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             raw_conv_bwd_data_dual(d1, dR[:, s1], w1, dsc, dS, ws, dx)
-        join_weight_grads()
+        sched.join_side()
         z = _zeros_like_or_none      # conv biases feed a BatchNorm: analytically zero gradient
         return (dx, None, None, dw1, z(b1, dR[:, s1]), dg1, de1, dw2, z(b2, dR[:, s2]), dg2, de2, dw3, z(b3, dR[:, s3]), dg3, de3,
                 dws, z(bs, dS), dgs, des, dgA, deA, dgB, deB)
@@ -1022,122 +848,110 @@ def _respath_bn_backward(dy, t, miB, gB, eB, slope, r3, mi3, g3, e3, r1, mi1, g1
     return a, b, (dgB, deB)
 
 
+def _respath_alloc(x, p, y=None):
+    """Descriptors and tensors of one ResPath3d body on x, allocated by the CURRENT stream.  y: where its output goes — None for a fresh tensor,
+    or a channel slice of a concat buffer (SkipJoinFn: cat[:, :Cs])."""
+    w3, w1 = p[0], p[4]
+    f32 = dict(dtype=torch.float32, device=x.device)
+    adt = act_dtype()
+    Cs = w3.shape[0]
+    d3, d1 = make_desc(x, w3, 1, adt), make_desc(x, w1, 1, adt)
+    dims = desc_out_dims(d3)
+    T = dict(adt=adt, Cs=Cs, d3=d3, d1=d1, dims=dims)
+    T["r3"] = torch.empty(_like_spatial(x, Cs, *dims), dtype=adt, device=x.device)
+    T["r1"] = torch.empty_like(T["r3"])
+    if y is not None and (y.shape != T["r3"].shape or y.dtype != adt):
+        raise _lib.DpiError("respath: the output slice is %s %s, the node writes %s %s" % (tuple(y.shape), y.dtype, tuple(T["r3"].shape), adt))
+    T["y"] = torch.empty_like(T["r3"]) if y is None else y
+    T["tless"] = _join_fused_ok(T["r3"])
+    T["mi3"], T["mi1"], T["miB"] = (torch.empty(2 * Cs, **f32) for _ in range(3))
+    T["ch13"] = torch.empty((2, 5 * Cs), **f32)
+    T["ch1"], T["ch3"], T["chB"] = T["ch13"][0], T["ch13"][1], torch.empty(5 * Cs, **f32)
+    # the join's sum t (None when it is not stored), and what the backward gets in its place: t, or the two chains it is re-formed from
+    # ([ch1, ch3], filled by _respath_launch)
+    T["t"] = None if T["tless"] else torch.empty_like(T["r3"])
+    T["keep"] = T["ch13"] if T["tless"] else T["t"]
+    return T
+
+
+def _respath_launch(x, rp, slope, p, T):
+    """The ResPath3d body on the current stream: conv3x3 / conv1x1 with statistics, residual join + statistics, bn -> T["y"]."""
+    (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = p
+    Do, Ho, Wo = T["dims"]
+    bn3_, bn1_ = rp.conv3x3._parts()[1], rp.conv1x1._parts()[1]
+    _cba_raw(T["d3"], x, None, w3, b3, bn3_, slope, T["r3"], T["mi3"], T["ch3"])
+    _cba_raw(T["d1"], x, None, w1, b1, bn1_, slope, T["r1"], T["mi1"], T["ch1"])
+    _join_forward(T["r1"], T["ch1"], T["r3"], T["ch3"], T["Cs"], Do * Ho * Wo, slope, rp.bn, gB, eB, T["miB"], T["y"], keep_t=not T["tless"],
+                  t=T["t"], ch_out=T["chB"])
+
+
+def _respath_save(ctx, x, T, p, slope):
+    _save_with_params(ctx, (x, T["r3"], T["r1"], T["keep"], T["mi3"], T["mi1"], T["miB"]), p)
+    ctx.descs = (T["d3"], T["d1"])
+    ctx.slope = float(slope)
+    ctx.tless = T["tless"]
+
+
+def _respath_backward(ctx, dy):
+    """Backward of the ResPath3d body a node saved with _respath_save, on the current stream (the caller joins the side streams).
+    Returns dx (None when x needs no gradient) and the gradients of the ten parameters in their order."""
+    (x, r3, r1, t, mi3, mi1, miB), (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = _saved_with_params(ctx, 7)
+    d3, d1 = ctx.descs
+    (dr3, dg3, de3), (dr1, dg1, de1), (dgB, deB) = _respath_bn_backward(dy, t, miB, gB, eB, ctx.slope, r3, mi3, g3, e3, r1, mi1, g1, e1, ctx.tless)
+    dw3, dw1 = torch.empty_like(w3), torch.empty_like(w1)
+    conv_bwd_weight_async(d3, x, None, dr3, dw3)
+    conv_bwd_weight_async(d1, x, None, dr1, dw1)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(x)
+        raw_conv_bwd_data_dual(d3, dr3, w3, d1, dr1, w1, dx)
+    z = _zeros_like_or_none
+    return dx, (dw3, z(b3, dr3), dg3, de3, dw1, z(b1, dr1), dg1, de1, dgB, deB)
+
+
 class ResPath3dFn(torch.autograd.Function):
     """ResPath3d (reference mulresunet.py:99-113) as one autograd node: y = bn(act(CBA1(x) + CBA3(x)))."""
 
     @staticmethod
     def forward(ctx, x, rp, slope, *p):
         x = _req(x, "respath input", act=True)
-        (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = p
-        L = _lib.load()
-        f32 = dict(dtype=torch.float32, device=x.device)
-        adt = act_dtype()
-        Ct = w3.shape[0]
-        bn3_, bn1_ = rp.conv3x3._parts()[1], rp.conv1x1._parts()[1]
-        d3, d1 = make_desc(x, w3, 1, adt), make_desc(x, w1, 1, adt)
-        Do, Ho, Wo = desc_out_dims(d3)
-        V = Do * Ho * Wo
-        r3 = torch.empty(_like_spatial(x, Ct, Do, Ho, Wo), dtype=adt, device=x.device)
-        r1 = torch.empty_like(r3)
-        mi3, mi1, miB = (torch.empty(2 * Ct, **f32) for _ in range(3))
-        ch13 = torch.empty((2, 5 * Ct), **f32)
-        ch1, ch3 = ch13[0], ch13[1]
-        _cba_raw(d3, x, None, w3, b3, bn3_, slope, r3, mi3, ch3)
-        _cba_raw(d1, x, None, w1, b1, bn1_, slope, r1, mi1, ch1)
-        y = torch.empty_like(r3)
-        tless = _join_fused_ok(r3, r1)
-        t = _join_forward(r1, ch1, r3, ch3, Ct, V, slope, rp.bn, gB, eB, miB, y, keep_t=not tless)
-        if tless:
-            t = ch13
-        ctx.tless = tless
-        ctx.save_for_backward(x, r3, r1, t, mi3, mi1, miB, *[q for q in p if q is not None])
-        ctx.none_mask = [q is None for q in p]
-        ctx.descs = (d3, d1)
-        ctx.slope = float(slope)
-        return y
+        T = _respath_alloc(x, p)
+        _respath_launch(x, rp, slope, p, T)
+        _respath_save(ctx, x, T, p, slope)
+        return T["y"]
 
     @staticmethod
     def backward(ctx, dy):
-        dy = _req(dy, "respath grad", act=True)
-        x, r3, r1, t, mi3, mi1, miB = ctx.saved_tensors[:7]
-        it = iter(ctx.saved_tensors[7:])
-        (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = [None if isnone else next(it) for isnone in ctx.none_mask]
-        d3, d1 = ctx.descs
-        slope = ctx.slope
-        (dr3, dg3, de3), (dr1, dg1, de1), (dgB, deB) = _respath_bn_backward(dy, t, miB, gB, eB, slope, r3, mi3, g3, e3, r1, mi1, g1, e1, ctx.tless)
-        dw3, dw1 = torch.empty_like(w3), torch.empty_like(w1)
-        conv_bwd_weight_async(d3, x, None, dr3, dw3)
-        conv_bwd_weight_async(d1, x, None, dr1, dw1)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            raw_conv_bwd_data_dual(d3, dr3, w3, d1, dr1, w1, dx)
-        join_weight_grads()
-        z = _zeros_like_or_none
-        return dx, None, None, dw3, z(b3, dr3), dg3, de3, dw1, z(b1, dr1), dg1, de1, dgB, deB
+        dx, grads = _respath_backward(ctx, _req(dy, "respath grad", act=True))
+        sched.join_side()
+        return (dx, None, None) + grads
 
 
 def _skip_alloc(x, p, Cd):
     """Tensors of one level join (ResPath3d(x) -> cat[:, :Cs], up-sampled deep branch -> cat[:, Cs:]), allocated by the CURRENT stream."""
-    (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = p
-    f32 = dict(dtype=torch.float32, device=x.device)
-    adt = act_dtype()
-    Cs = w3.shape[0]
-    d3, d1 = make_desc(x, w3, 1, adt), make_desc(x, w1, 1, adt)
-    Do, Ho, Wo = desc_out_dims(d3)
-    T = dict(adt=adt, Cs=Cs, Cd=Cd, d3=d3, d1=d1, dims=(Do, Ho, Wo))
-    T["r3"] = torch.empty(_like_spatial(x, Cs, Do, Ho, Wo), dtype=adt, device=x.device)
-    T["r1"] = torch.empty_like(T["r3"])
-    T["tless"] = _join_fused_ok(T["r3"])
-    T["mi3"], T["mi1"], T["miB"] = (torch.empty(2 * Cs, **f32) for _ in range(3))
-    T["ch13"] = torch.empty((2, 5 * Cs), **f32)
-    T["ch1"], T["ch3"], T["chB"] = T["ch13"][0], T["ch13"][1], torch.empty(5 * Cs, **f32)
-    # the join's sum t, or — when it is not stored — the two chains it is re-formed from ([ch1, ch3], filled by _skip_launch)
-    T["t"] = T["ch13"] if T["tless"] else torch.empty_like(T["r3"])
-    T["cat"] = torch.empty(_like_spatial(x, Cs + Cd, Do, Ho, Wo), dtype=adt, device=x.device)
+    Cs = p[0].shape[0]
+    _, D, H, W = _dims(x)
+    cat = torch.empty(_like_spatial(x, Cs + Cd, D, H, W), dtype=act_dtype(), device=x.device)
+    T = _respath_alloc(x, p, cat[:, :Cs])
+    T["cat"], T["Cd"] = cat, Cd
     return T
 
 
 def _skip_tensors(T):
-    return [T[k] for k in ("r3", "r1", "t", "mi3", "mi1", "miB", "ch13", "chB", "cat")]
-
-
-def _skip_launch(x, rp, slope, p, T):
-    """The ResPath half of the join on the current stream: conv3x3 / conv1x1 with statistics, residual join + statistics, bn -> cat[:, :Cs]."""
-    (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = p
-    L = _lib.load()
-    Cs = T["Cs"]
-    Do, Ho, Wo = T["dims"]
-    V = Do * Ho * Wo
-    bn3_, bn1_ = rp.conv3x3._parts()[1], rp.conv1x1._parts()[1]
-    _cba_raw(T["d3"], x, None, w3, b3, bn3_, slope, T["r3"], T["mi3"], T["ch3"])
-    _cba_raw(T["d1"], x, None, w1, b1, bn1_, slope, T["r1"], T["mi1"], T["ch1"])
-    nblk = L.dpi_stat_blocks(Cs, V)
-    part = torch.empty(nblk * Cs * 2, dtype=torch.float64, device=x.device)
-    tless = T["tless"]
-    check(L.dpi_chain_add_stats_io(ptr(T["r1"]), ptr(T["ch1"]), ptr(T["r3"]), ptr(T["ch3"]), Cs, V, slope, None if tless else ptr(T["t"]),
-                                   ptr(part), _io(T["r3"]), stream()), "dpi_chain_add_stats")
-    B = rp.bn
-    raw_bn_finalize(part, nblk, Cs, V, gB, eB, slope, B.running_mean, B.running_var, B.num_batches_tracked, T["miB"], T["chB"],
-                    act_first=1)
-    if tless:
-        check(L.dpi_chain_add_apply(ptr(T["r1"]), ptr(T["ch1"]), ptr(T["r3"]), ptr(T["ch3"]), ptr(T["chB"]), Cs, V, ptr(T["cat"][:, :Cs]),
-                                    _io(T["r3"]), stream()), "dpi_chain_add_apply")
-    else:
-        raw_chain_apply(T["t"], T["chB"], Cs, V, T["cat"][:, :Cs])
+    return [T[k] for k in ("r3", "r1", "keep", "mi3", "mi1", "miB", "ch13", "chB", "cat")]
 
 
 def skip_begin(x, rp, slope, Cd):
     """Start the ResPath half of a level join on the branch stream BEFORE the deeper U runs (it only needs the encoder output x).
     Returns the handle skip_join() takes, or None when the serial schedule applies."""
-    if not (branch_on() and BRANCH_SKIP) or x.ndim != 5:
+    if not (sched.branch_on() and sched.branch_skip) or x.ndim != 5:
         return None
     x = _req(x, "skip input", act=True)
     p = _cba_params(rp.conv3x3) + _cba_params(rp.conv1x1) + [rp.bn.weight, rp.bn.bias]
     with torch.no_grad():
         T = _skip_alloc(x, p, Cd)
-        with _Branch("skip", x, *_skip_tensors(T)):
-            _skip_launch(x, rp, slope, p, T)
+        with sched.branch("skip", x, *_skip_tensors(T)):
+            _respath_launch(x, rp, slope, p, T)
     return T
 
 
@@ -1152,7 +966,7 @@ class SkipTapFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        join_branch("skip")
+        sched.join_branch("skip")
         return g
 
 
@@ -1186,59 +1000,38 @@ class SkipJoinFn(torch.autograd.Function):
         if not (Do <= 2 * Dd and Ho <= 2 * Hd and Wo <= 2 * Wd):
             raise _lib.DpiError("skip_join: the up-sampled branch is smaller than the skip branch")
         if pre is None:
-            _skip_launch(x, rp, slope, p, T)
+            _respath_launch(x, rp, slope, p, T)
         cat = T["cat"]
         check(L.dpi_upsample2x_fwd_io(ptr(deep), None, Cd, Dd, Hd, Wd, Do, Ho, Wo, int(linear), ptr(cat[:, Cs:]), _io(deep), stream()),
               "dpi_upsample2x_fwd")
         if pre is not None:
-            join_branch("skip")          # the two producers wrote disjoint channel slices; the consumer needs both
-        ctx.save_for_backward(x, T["r3"], T["r1"], T["t"], T["mi3"], T["mi1"], T["miB"], *[q for q in p if q is not None])
-        ctx.none_mask = [q is None for q in p]
-        ctx.descs = (T["d3"], T["d1"])
-        ctx.slope = float(slope)
+            sched.join_branch("skip")          # the two producers wrote disjoint channel slices; the consumer needs both
+        _respath_save(ctx, x, T, p, slope)
         ctx.up = (Cs, Cd, Dd, Hd, Wd, Do, Ho, Wo, int(linear), deep.shape, deep.dtype)
         ctx.branched = pre is not None
-        ctx.tless = T["tless"]
         return cat
 
     @staticmethod
     def backward(ctx, dcat):
         dcat = _req(dcat, "skip-join grad", act=True)
-        x, r3, r1, t, mi3, mi1, miB = ctx.saved_tensors[:7]
-        it = iter(ctx.saved_tensors[7:])
-        (w3, b3, g3, e3, w1, b1, g1, e1, gB, eB) = [None if isnone else next(it) for isnone in ctx.none_mask]
-        d3, d1 = ctx.descs
-        slope = ctx.slope
         Cs, Cd, Dd, Hd, Wd, Do, Ho, Wo, linear, deep_shape, deep_dtype = ctx.up
         ddeep = None
         if ctx.needs_input_grad[1]:
             ddeep = torch.empty(deep_shape, dtype=deep_dtype, device=dcat.device)
             raw_upsample2x_bwd(dcat[:, Cs:], Cd, Dd, Hd, Wd, Do, Ho, Wo, linear, ddeep)
-
-        def respath_backward():
-            (dr3, dg3, de3), (dr1, dg1, de1), (dgB, deB) = _respath_bn_backward(dcat[:, :Cs], t, miB, gB, eB, slope,
-                                                                                  r3, mi3, g3, e3, r1, mi1, g1, e1, ctx.tless)
-            dw3, dw1 = torch.empty_like(w3), torch.empty_like(w1)
-            conv_bwd_weight_async(d3, x, None, dr3, dw3)
-            conv_bwd_weight_async(d1, x, None, dr1, dw1)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                raw_conv_bwd_data_dual(d3, dr3, w3, d1, dr1, w1, dx)
-            return dx, dw3, dg3, de3, dw1, dg1, de1, dgB, deB, _zeros_like_or_none(b3, dr3), _zeros_like_or_none(b1, dr1)
-
-        if ctx.branched and branch_on() and BRANCH_SKIP_BWD:
+        branched = bool(ctx.branched and sched.branch_on() and sched.branch_skip_bwd)
+        if branched:
             # the deeper U's backward (critical path, main stream) does not wait for this: SkipTapFn.backward joins, just before the
             # encoder block of the level consumes dx.  Tensors allocated in here come from the branch stream's pool.
-            with _Branch("skip", dcat, x, r3, r1, t, mi3, mi1, miB):
-                dx, dw3, dg3, de3, dw1, dg1, de1, dgB, deB, db3, db1 = respath_backward()
-            _defer(dg3, de3, dg1, de1, dgB, deB, db3, db1)
+            with sched.branch("skip", dcat, *ctx.saved_tensors[:7]):
+                dx, grads = _respath_backward(ctx, dcat[:, :Cs])
+            sched.defer(*grads[1:4], *grads[5:])        # (the two weight gradients: conv_bwd_weight_async noted them)
         else:
-            dx, dw3, dg3, de3, dw1, dg1, de1, dgB, deB, db3, db1 = respath_backward()
-        join_weight_grads()
+            dx, grads = _respath_backward(ctx, dcat[:, :Cs])
+        sched.join_side()
         if ctx.fan is not None and dx is not None:
-            ctx.fan.dx, ctx.fan.branched = dx, bool(ctx.branched and branch_on() and BRANCH_SKIP_BWD)
-        return dx, ddeep, None, None, None, None, None, dw3, db3, dg3, de3, dw1, db1, dg1, de1, dgB, deB
+            ctx.fan.dx, ctx.fan.branched = dx, branched
+        return (dx, ddeep, None, None, None, None, None) + grads
 
 
 class LeakyReLUFn(torch.autograd.Function):
@@ -1506,7 +1299,7 @@ class PartialConvFn(torch.autograd.Function):
             check(L.dpi_pconv_mask_bwd(ptr(dx), ptr(x), ptr(m), Cin, Cm, V, ptr(dx), ptr(dm), stream()), "dpi_pconv_mask_bwd")
             if not ctx.needs_input_grad[0]:
                 dx = None
-        join_weight_grads()
+        sched.join_side()
         return dx, dm, dw, db
 
 

@@ -41,7 +41,7 @@ class _FusedMultiTensor(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none=True):
         """Gradients are always dropped, never zeroed in place: the fused nodes hand autograd freshly written tensors which AccumulateGrad adopts
-        as .grad (no copy, no add pass); with the once-per-step join (ops.JOIN_AT) a surviving .grad would be accumulated into on the main stream
+        as .grad (no copy, no add pass); with the once-per-step join (ops.sched.join_at) a surviving .grad would be accumulated into on the main stream
         before the side stream has produced the new gradient."""
         if not set_to_none:
             raise _lib.DpiError("%s.zero_grad(set_to_none=False) is not supported: gradients are adopted, not accumulated (ops.finish_backward)" % self._name)

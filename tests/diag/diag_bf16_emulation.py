@@ -43,7 +43,7 @@ def main():
         orig_raw(d, xx, in_chain, w, b, bn, slope, r_out, mi_out, chain_out)
         raw_hip[name_of[w.data_ptr()][:-len(".weight")]] = (r_out.detach().float().cpu(), mi_out.detach().float().cpu())
     ops._cba_raw = rec_raw
-    ops.BRANCH_SKIP = False
+    ops.sched.branch_skip = False
     with T.precision_scope():
         out = T.net(x.cuda().to(BF)).float().cpu()
     ops.conv_bn_act = orig_cba

@@ -229,7 +229,7 @@ def test_addon_in_the_loop_big_patch(precision):
     T = _interp3d(["--aa_weight", "0.5", "--aa_smooth", "2"], 3, (128, 128, 64), precision=precision)
     assert T.wants_weight_grad_overlap() and not T.graph_capable()
     T.optimize(verbose=False)
-    assert ops._deferred == []
+    assert ops.sched.deferred == []
     h = T.history
     assert len(h) == 3 and np.isfinite(h.loss).all() and np.isfinite(h.reg).all()
     # iteration 0 alone again to read its output (optimize keeps the best one)

@@ -364,7 +364,7 @@ def test_deferred_gradients_must_be_adopted_by_autograd():
     try:
         T.optimizer.zero_grad()
         T.optimization_loop()                                   # clean iteration: every deferred gradient is a parameter's .grad
-        assert not ops._in_iteration[0] and not ops._deferred
+        assert not ops.sched.in_iteration and not ops.sched.deferred
         w = next(p for p in T.net.parameters() if p.ndim == 5)
         g_clean = w.grad.clone()
         for p in T.net.parameters():                             # what zero_grad(set_to_none=False) leaves behind
@@ -372,7 +372,7 @@ def test_deferred_gradients_must_be_adopted_by_autograd():
                 p.grad = torch.zeros_like(p.grad)
         with pytest.raises(_lib.DpiError, match="side / branch stream"):
             T.optimization_loop()
-        assert not ops._in_iteration[0] and not ops._deferred and not ops._side_keep
+        assert not ops.sched.in_iteration and not ops.sched.deferred and not ops.sched.side_keep
         T.optimizer.zero_grad()
         T.optimization_loop()
         assert torch.isfinite(w.grad).all() and w.grad.shape == g_clean.shape
@@ -393,7 +393,7 @@ def test_an_iteration_that_raises_leaves_no_iteration_state_behind(monkeypatch):
         monkeypatch.setattr(ops, "masked_loss", boom)
         with pytest.raises(RuntimeError, match="boom"):
             T.optimization_loop()
-        assert not ops._in_iteration[0] and not ops._side_keep and not ops._deferred and not ops._branch_open[0]
+        assert not ops.sched.in_iteration and not ops.sched.side_keep and not ops.sched.deferred and not ops.sched.branch_open
     finally:
         ops.set_weight_grad_overlap(False)
 

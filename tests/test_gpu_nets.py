@@ -389,14 +389,14 @@ def test_fused_block_nodes_match_leaf_by_leaf_execution(shape, upsample, overlap
     res = []
     for fused, n in ((True, net), (False, net2)):
         M.FUSE_BLOCKS = fused
-        ops.OVERLAP_WEIGHT_GRADS = overlap and fused      # weight gradients on the side stream (joined per node)
+        ops.sched.overlap = overlap and fused      # weight gradients on the side stream (joined per node)
         try:
             out = n(z)
             loss, _ = ops.masked_loss(out, img, mask, "mse")
             loss.backward()
         finally:
             M.FUSE_BLOCKS = True
-            ops.OVERLAP_WEIGHT_GRADS = False
+            ops.sched.overlap = False
         torch.cuda.synchronize()
         res.append((out.detach(), float(loss.detach()), {k: p.grad.detach() for k, p in n.named_parameters() if p.grad is not None},
                     {k: b.detach().clone() for k, b in n.named_buffers()}))
@@ -421,7 +421,7 @@ def test_fused_block_nodes_match_leaf_by_leaf_execution(shape, upsample, overlap
 
 @pytest.mark.parametrize("shortcut,precision", [(0, "fp32"), (1, "fp32"), (2, "fp32"), (0, "bf16"), (2, "bf16")])
 def test_branch_stream_schedule_is_bit_identical_to_the_serial_one(monkeypatch, shortcut, precision):
-    """Round 5: weight gradients joined once per step (ops.JOIN_AT = "step"), the ResPath half of every level join — forward and
+    """Round 5: weight gradients joined once per step (ops.sched.join_at = "step"), the ResPath half of every level join — forward and
     backward — on the branch stream (ops.skip_begin / SkipTapFn), optionally the 1x1x1 shortcuts too.  Same kernels on the same
     operands in the same per-tensor order: losses, SNR, best output and every weight after 4 Adam iterations must equal the serial
     schedule (per-node joins, no branch stream) BIT FOR BIT — a missing stream dependency shows up as a difference (or NaN).
@@ -438,10 +438,10 @@ def test_branch_stream_schedule_is_bit_identical_to_the_serial_one(monkeypatch, 
     mask = u.random_trace_mask(shape, 0.6, seed=5)[..., None].astype(np.float64)
 
     def run(join_at, branch, fan_in):
-        monkeypatch.setattr(ops, "JOIN_AT", join_at)
-        monkeypatch.setattr(ops, "BRANCH_STREAMS", branch)
+        monkeypatch.setattr(ops.sched, "join_at", join_at)
+        monkeypatch.setattr(ops.sched, "branch_streams", branch)
         monkeypatch.setattr(ops, "FAN_IN", fan_in)
-        monkeypatch.setattr(ops, "BRANCH_SHORTCUT", shortcut)
+        monkeypatch.setattr(ops.sched, "branch_shortcut", shortcut)
         u.set_seed(0)
         T = Interpolator(args, "/tmp")
         T.load_data({"image": vol, "mask": mask, "name": "0"})
@@ -468,7 +468,7 @@ def test_branch_stream_schedule_is_bit_identical_to_the_serial_one(monkeypatch, 
         for k in range(4):          # a race need not show up in every run; the last run: the streams without the fused fan-in
             fan = k < 3
             got = run("step", True, fan)
-            assert ops.OVERLAP_WEIGHT_GRADS and not ops._in_iteration[0] and not ops._side_keep
+            assert ops.sched.overlap and not ops.sched.in_iteration and not ops.sched.side_keep
             same(serial[fan], got)
         l0 = serial[False][0]
     finally:

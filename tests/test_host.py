@@ -326,15 +326,15 @@ def test_branch_stream_host_logic_knows_the_deep_branch_width(monkeypatch):
     walk(net)
     assert seen == 4                                            # four level joins in the default five-scale net
     # the switch as a fresh process has it: a big-patch GPU test earlier in the same session may have left it on (ops.set_weight_grad_overlap)
-    monkeypatch.setattr(ops, "OVERLAP_WEIGHT_GRADS", os.environ.get("DPI_OVERLAP_WGRAD", "0") == "1")
-    assert ops.JOIN_AT == "step" and not ops._in_iteration[0]
-    assert not ops.branch_on()                                  # no iteration, no weight-gradient overlap: the serial schedule
+    monkeypatch.setattr(ops.sched, "overlap", os.environ.get("DPI_OVERLAP_WGRAD", "0") == "1")
+    assert ops.sched.join_at == "step" and not ops.sched.in_iteration
+    assert not ops.sched.branch_on()                                  # no iteration, no weight-gradient overlap: the serial schedule
     ops.begin_iteration()
     try:
-        assert ops._in_iteration[0] and not ops.branch_on()     # still off: the overlap is only switched on for >= 2^20-voxel patches on a GPU
+        assert ops.sched.in_iteration and not ops.sched.branch_on()     # still off: the overlap is only switched on for >= 2^20-voxel patches on a GPU
     finally:
         ops.finish_backward()
-    assert not ops._in_iteration[0] and not ops._side_keep
+    assert not ops.sched.in_iteration and not ops.sched.side_keep
 
 
 def test_polyphase_identity_behind_design_section_7():
