@@ -366,7 +366,12 @@ int dpi_deconv4x4s2_bwd_weight(const float* x, const float* dy, int Cin, int Cou
  * Replaces main.py:161-167: loss = mean(|out*m - img*m|) (kind 0, L1) or mean((.)^2) (kind 1, MSE)
  * over all n elements; dout = dloss/dout * grad_scale; plus the sums for snr/pcorr
  * (utils/metrics.py:15,32-36).  ws: double[dpi_loss_ws_doubles(n)].
- * result (device, double[8]): {loss, snr_dB, pcorr, sum_t2, sum_(t-o)^2, sum_o, sum_t, reserved}.
+ * result (device, double[8]): {loss, snr_dB, pcorr, sum_t2, sum_(t-o)^2, sum_o, sum_t, sum_o2}; all eight are written.
+ * Extents (tests/test_gpu_iteration_contract.py holds every launch to them, inside guard bands): dpi_loss_ws_doubles(n) = 8 * 1024 for
+ * every n — the grid is min(ceil(n / 2048), 1024) blocks and block b writes ws[8 b .. 8 b + 6] only; nothing is read or written past
+ * result[7].  Per element, in fp32: d = out*mask - img*mask, inv_n = grad_scale / (float)n, dout = ((2 d) mask) inv_n (MSE) or
+ * (sign(d) mask) inv_n (L1); dout may be NULL (no gradient is stored, the result is the same bit for bit).  The sums are accumulated in
+ * double in a fixed order: two launches on the same data give the same bits.
  */
 size_t dpi_loss_ws_doubles(size_t n);
 int dpi_masked_loss(const float* out, const float* img, const float* mask, size_t n, int kind,
@@ -377,7 +382,7 @@ int dpi_masked_loss(const float* out, const float* img, const float* mask, size_
  * and accumulation order; neither mask is materialised — and the pass adds, with e = t - o:
  *   result[8] = val_loss = sum |e m_ho| (kind 0) or sum (e m_ho)^2 (kind 1), divided by N_ho;
  *   result[9] = val_snr  = 10 log10(sum (t m_ho)^2 / sum (e m_ho)^2);   result[10] = N_ho = number of samples with m_ho != 0.
- * result: double[11].  ws: double[2 * dpi_loss_ws_doubles(n)]. */
+ * result: double[11], all written.  ws: double[2 * dpi_loss_ws_doubles(n)] (block b writes ws[16 b .. 16 b + 11]). */
 int dpi_masked_loss_holdout(const float* out, const float* img, const float* mask, const float* sel, int C, int T, size_t S,
                             int kind, float grad_scale, float* dout, double* ws, double* result, void* stream);
 
@@ -401,6 +406,14 @@ int dpi_ema_loss(const float* out, float* avg, const float* img, const float* ma
  * step_lr (device, float[2]): {step count as float (already incremented), lr}.  `active` (device int,
  * may be NULL): when *active == 0 the update is skipped (device-side early stop).  Betas/eps are doubles so that
  * 1-beta and the bias corrections are derived in double and then rounded, exactly as torch does on the host.
+ * Rounding points (the library is built with -ffp-contract=off; tests/iteration_cases.py adam_np restates them and
+ * tests/test_gpu_iteration_contract.py holds p, m and v to that restatement bit for bit):
+ *   omb1 = (float)(1 - beta1), omb2 = (float)(1 - beta2), step_size = (float)(lr / (1 - beta1^step)), bc2s = (float)sqrt(1 - beta2^step),
+ *   with lr the fp32 step_lr[1] widened to double, and beta2, eps rounded to fp32; then per element, every operation in fp32:
+ *   m = m + omb1 * (g - m);   v = beta2 * v + (omb2 * g) * g;   p = p - step_size * (m / (sqrt(v) / bc2s + eps)).
+ * torch's CPU kernels fuse the multiply-adds of lerp_ / addcmul_ and form (step_size * m) / denom: against torch.optim.Adam one step
+ * differs by at most 1 ulp in m and v and 5 ulp of max(|p|, |update|) in p (measured, tests/test_iteration_refs_host.py).
+ * ntensors must lie in [1, 65535] (it is a grid dimension).  Accesses are scalar: a row may start at any element offset.  g is only read.
  */
 typedef struct { float* p; const float* g; float* m; float* v; } dpi_adam_tensor;
 int dpi_adam_multi(const dpi_adam_tensor* tensors, const int64_t* sizes, int ntensors,
@@ -433,6 +446,10 @@ int dpi_moments_update(const float* out, float* mean, float* m2, size_t n, const
  * replayed without host synchronisation: appends {loss, snr, pcorr, lr} to hist[iter], raises *improved when
  * loss <= loss_min (best-output tracking), runs ReduceLROnPlateau(mode=min, rel threshold) on step_lr[1] and
  * EarlyStopping(percentage) / NaN stop on *active.  state: double[8], zero-initialised except state[2] = +inf.
+ * hist: double[4 * max_iters]; a call with state[0] >= max_iters writes no row and still advances state[0].  *active == 0 on entry:
+ * state, hist and step_lr stay bit for bit as they were and *improved is set to 0.  A tie (loss == loss_min) improves: the later
+ * iterate wins.  A NaN loss never improves; it stops the run only with es_patience != 0 and from the second call on (the first call's
+ * loss becomes es_best unexamined, as in utils/torch.py).
  * dpi_copy_if copies src -> dst only when *flag != 0 (keeps out_best on the device). */
 int dpi_loop_control(const double* metrics, double* state, double* hist, int max_iters, float* step_lr,
                      int* active, int* improved, int use_plateau, double factor, double threshold,
@@ -466,6 +483,11 @@ int dpi_copy_if(const int* flag, const float* src, float* dst, size_t n, void* s
  * Replaces main.py:148-150: out = z + std * N(0,1), Philox4x32-10 + Box-Muller, counter = element index,
  * key = (seed, *step_ptr) so that every replay of a captured graph draws fresh noise.
  * step_ptr (device, uint64) may be NULL (then step = 0).
+ * The stream, as tests/iteration_cases.py restates it on the host: elements 4q .. 4q+3 come from ONE Philox4x32-10 block with counter
+ * words {q lo, q hi, stream lo, stream hi} (stream = *step_ptr, or stream_id for dpi_fill_normal) and key {seed lo, seed hi}; Box-Muller
+ * on the four output words c0..c3: r0 = sqrt(-2 ln(((c0 >> 8) + 1) / 2^24)), a0 = 2 pi (c1 >> 8) / 2^24, likewise r1, a1 from c2, c3;
+ * the four normals are r0 cos a0, r0 sin a0, r1 cos a1, r1 sin a1, and out = fma(std, normal, z or mean).  n % 4 != 0 and n % 4 == 0
+ * draw the same values.  The float4 path is chosen from n % 4 alone (the precondition above dpi_bn_*).
  */
 int dpi_noise_add(const float* z, size_t n, float std, uint64_t seed, const uint64_t* step_ptr,
                   float* out, void* stream);
@@ -487,6 +509,11 @@ int dpi_axpy(float a, const float* x, size_t n, float* y, void* stream);
  * Replaces PatchExtractor.reconstruct (utils/patch_extractor.py:395-428): overlap-add of one patch
  * (pd,ph,pw) at origin (od,oh,ow) into acc[D][H][W]; dpi_overlap_normalize divides by the analytic hit
  * count of the regular window grid and by `gain` (data.py:116).
+ * dpi_overlap_add: acc += patch, one fp32 addition per sample, in launch order on one stream; a patch reaching outside the volume is
+ * refused.  dpi_overlap_normalize: acc = acc / ((float)count * gain) with count the number of windows {k * stride : 0 <= k * stride <=
+ * N - p} per axis that cover the sample, multiplied over the axes; gain == 0 and a stride <= 0 are refused.  A sample that no window
+ * covers — the far end of an axis with (N - p) % stride != 0 — has count 0 and gets acc / 0: +-inf, or NaN where acc is 0.  The callers
+ * use window grids that cover the volume; the weighted pair below writes 0 there instead.
  */
 int dpi_overlap_add(const float* patch, int pd, int ph, int pw, int od, int oh, int ow, float* acc,
                     int D, int H, int W, void* stream);
