@@ -131,6 +131,12 @@ SIGNATURES = {
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "dpi_trace_sample_adj": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    # --trace_interp (ours): (kind), (off, kind, X, Y, w) on HOST pointers, w = [2][K][X][Y], then (x, w, off, K, C, T, X, Y, y, stream) and
+    # (y, w, off, K, C, T, X, Y, x, stream) on the device.  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_trace_interp_taps": (_I, [_I]),
+    "dpi_trace_interp_weights": (_I, [_P, _I, _I, _I, _P]),
+    "dpi_trace_resample_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "dpi_trace_resample_adj": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "dpi_max_ws_floats": (_Z, [_Z]),
     "dpi_scaled_max": (_I, [_P, _Z, _F, _P, _P, _P]),
     "dpi_threshold": (_I, [_P, _Z, _P, _P, _P]),

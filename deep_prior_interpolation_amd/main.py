@@ -50,6 +50,7 @@ class Interpolator:
         self._avo_op = None                                      # built per patch length T (net_forward)
         # --trace_offsets (ours): the loss sees the grid output sampled at the recorded trace positions (data_forward)
         self.trace_offsets_file = check_trace_offsets_flag(args)
+        self.trace_interp = getattr(args, "trace_interp", None) or "linear"     # --trace_interp: the kernel R samples with (linear = bilinear)
         self.trace_offsets = None                                # per patch: (X, Y, 2) as used, i.e. zero at unknown traces
         self._sampling_op = None                                 # per patch: TraceSampling, its offsets on the device (load_data)
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
@@ -127,7 +128,7 @@ class Interpolator:
         self.trace_offsets = off * known[..., None].astype(np.float32)
         from .operators import TraceSampling
         try:
-            self._sampling_op = TraceSampling(np.moveaxis(self.trace_offsets, -1, 0))       # [2][X][Y]
+            self._sampling_op = TraceSampling(np.moveaxis(self.trace_offsets, -1, 0), interp=self.trace_interp)       # [2][X][Y]
         except ValueError as e:
             raise ValueError("--trace_offsets: %s" % e) from e
         self._sampling_op.upload(self.device)
@@ -853,6 +854,7 @@ class Interpolator:
             run.update(avo_theta=list(self.avo[0]), avo_vsvp=self.avo[1], avo_linearization=self.avo[2], avo_model=self.avo_model())
         if self.trace_offsets_file is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
+            run["trace_interp"] = self.trace_interp
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)

@@ -135,6 +135,10 @@ _FLAGS = [
                                     "(|d| <= 0.5; absent = off): (X, Y, 2) = dx, dy for --datadim 3d on a (T, X, Y) volume, (X,) or (X, 1) = dx "
                                     "for --datadim 2d on a (T, X) section.  The loss then compares the traces with the network's grid output "
                                     "sampled bilinearly at those positions; what is selected and saved stays the regular-grid output")),
+    (("--trace_interp",), dict(type=str, required=False, default="linear", choices=["linear", "cubic", "sinc8"],
+                              help="ours: how --trace_offsets samples the grid output at the recorded positions: linear = 2 taps per axis "
+                                   "(bilinear), cubic = 4 taps (Keys, a = -1/2), sinc8 = 8 taps (Kaiser-windowed sinc).  The wider kernels "
+                                   "keep more of the spatial wavenumbers close to aliasing; needs --trace_offsets")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -178,7 +182,13 @@ def check_trace_offsets_flag(args: Namespace):
     """--trace_offsets and what it cannot be combined with; returns the file name, or None when it is off (also for a Namespace without the
     key, as those of older args.txt files).  The file itself is read and checked by data.extract_patches."""
     name = getattr(args, "trace_offsets", None)
+    interp = getattr(args, "trace_interp", None) or "linear"
+    if interp not in ("linear", "cubic", "sinc8"):
+        raise ValueError("--trace_interp must be linear, cubic or sinc8, got %r" % (interp,))
     if name is None:
+        if interp != "linear":
+            raise ValueError("--trace_interp %s needs --trace_offsets: without offsets nothing is sampled and the flag would silently do "
+                             "nothing" % interp)
         return None
     if getattr(args, "avo_theta", None) is not None:
         raise ValueError("--trace_offsets does not combine with --avo_theta, which needs --datadim 2.5d")
@@ -284,6 +294,9 @@ def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
     # --trace_offsets (ours) decides what the weights were fitted to; args.txt files of older runs lack the key: off
     if a.get("trace_offsets") != b.get("trace_offsets"):
         errors.append("trace_offsets")
+    # --trace_interp (ours) decides the operator the weights were fitted through; an args.txt without the key: linear
+    if (a.get("trace_interp") or "linear") != (b.get("trace_interp") or "linear"):
+        errors.append("trace_interp")
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

@@ -593,6 +593,35 @@ int dpi_avo_adj(const float* y, const float* G, int ntheta, int T, size_t S, flo
 int dpi_trace_sample_fwd(const float* x, const float* off, int C, int T, int X, int Y, float* y, void* stream);
 int dpi_trace_sample_adj(const float* y, const float* off, int C, int T, int X, int Y, float* x, void* stream);
 
+/* ---------------------------------------------------------------- Trace sampling with K x K taps (--trace_interp) --
+ * Ours.  The bilinear R above is a low-pass filter whose strength depends on the offset (a zero at the spatial Nyquist wavenumber for
+ * d = 0.5); these entry points apply R from a table of per-trace weights with K taps per axis.  Kinds 0 / 1 / 2 = linear / cubic /
+ * sinc8, K = 2 / 4 / 8 (dpi_trace_interp_taps; -1 for an unknown kind).
+ * Tap geometry, per axis of n nodes, trace on node i with offset d: the first tap is i - K/2 + 1 when d >= 0, else i - K/2; tap k in
+ * [0, K) sits at clamp(first + k, 0, n - 1); taps that clamp onto one node all count.  Tap indices never depend on the size of d (the
+ * offsets are read for their sign only), and K = 2 is exactly the geometry of dpi_trace_sample_*.
+ * Weights w(u) at u = (first + k) - (i + d), in float64 from the fp32 offset, rounded to fp32 once:
+ *     linear  1 - |u|
+ *     cubic   Keys, a = -1/2: 1.5|u|^3 - 2.5|u|^2 + 1 for |u| <= 1, -0.5|u|^3 + 2.5|u|^2 - 4|u| + 2 for 1 < |u| < 2
+ *             (d = 0.5: -1/16, 9/16, 9/16, -1/16; reproduces polynomials up to degree 2 away from the edges)
+ *     sinc8   sinc(u) * I0(beta * sqrt(1 - (u/4)^2)) / I0(beta), beta = 6, divided by the sum of the eight values (weights sum to 1)
+ * d == 0 gives the unit weight on the trace's own node and exact zeros elsewhere for every kind, and w(-d)[k] = w(d)[K - 1 - k] exactly.
+ *     dpi_trace_interp_weights: host pointers; off = [2][X][Y] (plane 0 dx, plane 1 dy) -> w = [2][K][X][Y]: axis, then tap, then trace.
+ *                               DPI_E_ARG for null pointers, non-positive sizes or an unknown kind.
+ *     dpi_trace_resample_fwd:   y[c][t][x][y] = sum_kx w[0][kx][x][y] * (sum_ky w[1][ky][x][y] * in[c][t][tap_x][tap_y]) in fp32, ky
+ *                               ascending inside, kx ascending outside.  For Y = 1 every y tap is the one node and the inner sum is
+ *                               taken as (w[1][0] + ... + w[1][K-1]) * in: K taps, not K^2 (the factor is 1 exactly for dy = 0).
+ *     dpi_trace_resample_adj:   the exact transpose as a gather: node (x', y') collects from the (K + 1) x (K + 1) traces around it those
+ *                               of their clamped taps that land on it.  No atomics, sums in a fixed order: deterministic, and
+ *                               independent of the launch shape.
+ * Device tensors [C][T][X][Y] fp32 as for dpi_trace_sample_*, w and off on the device, any 4-byte aligned pointers.  K is 2, 4 or 8;
+ * another K, null pointers, in == out, a non-positive size and more than 2^60 elements return an error before any launch.  Zero
+ * offsets make both the identity bit for bit.  ABI version stays: a stale library fails on the unresolved symbols. */
+int dpi_trace_interp_taps(int kind);
+int dpi_trace_interp_weights(const float* off, int kind, int X, int Y, float* w);
+int dpi_trace_resample_fwd(const float* x, const float* w, const float* off, int K, int C, int T, int X, int Y, float* y, void* stream);
+int dpi_trace_resample_adj(const float* y, const float* w, const float* off, int K, int C, int T, int X, int Y, float* x, void* stream);
+
 /* ---------------------------------------------------------------- POCS regulariser --------------
  * Replaces utils/pocs.py:5-19 (threshold / compute_threshold: out = max(x) * scale with scale = perc/100, kept on the device;
  * y = x * ((x > th) + (x < -th)) on the real view of the spectrum) and :80-84 (y = weighted_data + weighted_mask * x).

@@ -1,0 +1,331 @@
+"""--trace_interp on the GPU: dpi_trace_resample_fwd / dpi_trace_resample_adj against the float64 restatement of tests/trace_interp_cases.py,
+the whole operator as a matrix, the operator's properties, the entry points' refusals, and the deep-prior loop with the operator between
+the network and the loss."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import trace_sampling_cases as lin
+from trace_interp_cases import (OFFSET_KINDS, SHAPE_IDS, SHAPES, TAPS, U23, adjoint64, adjoint_tolerance, dense_matrix, forward64,
+                                forward_tolerance, offsets_for, structure)
+
+from deep_prior_interpolation_amd import _lib, utils as u
+from deep_prior_interpolation_amd.operators import TraceSampling, dottest, interp_weights
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+WIDE = ["cubic", "sinc8"]
+
+
+def _vectors(shape, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randn((1,) + shape, generator=gen), torch.randn((1,) + shape, generator=gen)
+
+
+def _tensor_shape(shape):
+    """(C, T, X, Y) -> the tensor the operator sees: Y = 1 is the 2-D layout (1, C, T, X)."""
+    return (1,) + (shape[:3] if shape[3] == 1 else shape)
+
+
+def _check(got, ref, tol, what):
+    err = float(np.abs(got.detach().cpu().numpy().astype(np.float64).reshape(ref.shape) - ref).max())
+    print("%s: worst error / tolerance = %.3f" % (what, err / tol))
+    assert err <= tol, (what, err, tol)
+
+
+_REF = {}
+
+
+def _reference(shape, kind, interp):
+    """(x, y, off, table, R x, R^T y, forward tolerance, adjoint tolerance) of a case, computed once and shared by the tests that need it."""
+    key = (shape, kind, interp)
+    if key not in _REF:
+        x, y = _vectors(shape, seed=SHAPES.index(shape))
+        off = offsets_for(kind, shape[2], shape[3], seed=1 + SHAPES.index(shape))
+        w = interp_weights(off, interp)
+        _REF[key] = (x, y, off, w, forward64(x[0].numpy(), off, interp), adjoint64(y[0].numpy(), off, interp),
+                     forward_tolerance(w, x.numpy()), adjoint_tolerance(off, w, y.numpy()))
+    return _REF[key]
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("kind", OFFSET_KINDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_forward_and_adjoint_against_float64(shape, kind, interp):
+    """Forward (K^2 + 2) * 2^-23 * A * max|x|, adjoint (n + 2) * 2^-23 * B * max|y|: A, n and B counted by the restatement for the case."""
+    x, y, off, _, fwd, adj, tol_f, tol_a = _reference(shape, kind, interp)
+    op = TraceSampling(off, interp=interp)
+    view = _tensor_shape(shape)
+    got = op.forward(x.view(view).to(DEV))
+    assert tuple(got.shape) == view
+    _check(got, fwd, tol_f, "forward")
+    got = op.adjoint(y.view(view).to(DEV))
+    assert tuple(got.shape) == view
+    _check(got, adj, tol_a, "adjoint")
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("kind", ["random", "plus_half", "minus_half"])
+@pytest.mark.parametrize("grid", [(1, 1), (3, 1), (67, 1), (5, 7), (9, 12)], ids=["1x1", "3x1", "67x1", "5x7", "9x12"])
+def test_the_whole_operator_as_a_matrix(grid, kind, interp):
+    """The N x N identity as C = 1, T = N (row t an impulse at node t): one forward launch gives the matrix (transposed: row t, trace s holds
+    M[s][t]), one adjoint launch its transpose.  Entry by entry against the restatement's dense matrix: every non-zero within 4 * 2^-23
+    relative, every structural zero (no tap of the trace on the node) and every entry the restatement has as 0 exactly 0.  A dropped or
+    misplaced tap of weight 4e-5 shows here; in a max-error test it would not."""
+    X, Y = grid
+    N = X * Y
+    off = offsets_for(kind, X, Y, seed=9)
+    M = dense_matrix(off, interp)
+    hit = structure(off, TAPS[interp])
+    assert not M[~hit].any()
+    eye = torch.eye(N, device=DEV).view(_tensor_shape((1, N, X, Y)))
+    op = TraceSampling(off, interp=interp)
+    for what, got, ref in (("forward", op.forward(eye), M.T), ("adjoint", op.adjoint(eye), M)):
+        got = got.cpu().numpy().astype(np.float64).reshape(N, N)
+        zero = ref == 0
+        assert not got[zero].any(), "%s: %d entries that must be 0 are not" % (what, int(np.count_nonzero(got[zero])))
+        rel = np.abs(got[~zero] - ref[~zero]) / np.abs(ref[~zero])
+        print("%s: %d non-zeros, worst relative error / (4 * 2^-23) = %.3f" % (what, rel.size, rel.max() / (4 * U23)))
+        assert rel.max() <= 4 * U23, (what, rel.max())
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_two_taps_with_a_linear_table_against_the_bilinear_entry_points(shape):
+    """K = 2 through the new entry points, table = the linear weights, against dpi_trace_sample_fwd / _adj within the linear tolerance."""
+    x, y = _vectors(shape, seed=SHAPES.index(shape))
+    off = offsets_for("random", shape[2], shape[3], seed=1 + SHAPES.index(shape))
+    L = _lib.load()
+    C_, T_, X_, Y_ = shape
+    offd, wd = torch.from_numpy(off).to(DEV), torch.from_numpy(interp_weights(off, "linear")).to(DEV)
+    for new, old, src, n_terms, what in ((L.dpi_trace_resample_fwd, L.dpi_trace_sample_fwd, x, lin.N_TERMS_FWD, "forward"),
+                                         (L.dpi_trace_resample_adj, L.dpi_trace_sample_adj, y, lin.N_TERMS_ADJ, "adjoint")):
+        srcd = src.to(DEV)
+        a, b = torch.full_like(srcd, 3.0), torch.full_like(srcd, 4.0)
+        _lib.check(new(_lib.ptr(srcd), _lib.ptr(wd), _lib.ptr(offd), 2, C_, T_, X_, Y_, _lib.ptr(a), _lib.stream()), what)
+        _lib.check(old(_lib.ptr(srcd), _lib.ptr(offd), C_, T_, X_, Y_, _lib.ptr(b), _lib.stream()), what)
+        _check(a, b.cpu().numpy().astype(np.float64), lin.tolerance(n_terms, src.numpy()), what)
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_views_off_16_byte_alignment_inside_guard_bands(shape, interp):
+    """Input, table, offsets and output each moved one float off their allocation's alignment; the floats around the output stay untouched."""
+    x, y, off, w, fwd, adj, tol_f, tol_a = _reference(shape, "random", interp)
+    L = _lib.load()
+    C_, T_, X_, Y_ = shape
+
+    def view(t, guard=8):
+        buf = torch.full((t.numel() + 1 + guard,), 777.0, device=DEV)
+        v = buf[1:1 + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return buf, v
+
+    _, off_dev = view(torch.from_numpy(off))
+    _, w_dev = view(torch.from_numpy(w))
+    for fn, src, ref, tol, what in ((L.dpi_trace_resample_fwd, x, fwd, tol_f, "forward"), (L.dpi_trace_resample_adj, y, adj, tol_a, "adjoint")):
+        _, vin = view(src)
+        obuf, got = view(torch.zeros(src.shape))
+        _lib.check(fn(_lib.ptr(vin), _lib.ptr(w_dev), _lib.ptr(off_dev), TAPS[interp], C_, T_, X_, Y_, _lib.ptr(got), _lib.stream()), what)
+        torch.cuda.synchronize()
+        assert bool((obuf[:1] == 777.0).all()) and bool((obuf[1 + got.numel():] == 777.0).all())
+        _check(got, ref, tol, what)
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_zero_offsets_are_the_identity_bit_for_bit(shape, interp):
+    x, _, off, _, _, _, _, _ = _reference(shape, "zero", interp)
+    op = TraceSampling(off, interp=interp)
+    xd = x.view(_tensor_shape(shape)).to(DEV)
+    assert torch.equal(op.forward(xd), xd) and torch.equal(op.adjoint(xd), xd)
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
+def test_dottest(shape, interp):
+    """dottest's relative error divides by the dot product itself, which for two random vectors is a sum of n terms of either sign: about
+    |d| |R^T r| / sqrt(n), but now and then far smaller (1x3x9x12, seed 3, sinc8: 0.038 where 16.7 is typical, and fp32 rounding alone is
+    then 5e-5 of it).  So the vectors are drawn with the first seed from 3 on for which the float64 restatement's dot product reaches half
+    its typical size: decided by the restatement alone, before anything runs on the device."""
+    off = offsets_for("random", shape[2], shape[3], seed=1 + SHAPES.index(shape))
+    view = _tensor_shape(shape)
+    for seed in range(3, 40):
+        gen = torch.Generator().manual_seed(seed)
+        d1, r1 = (torch.randn(view, generator=gen).numpy().astype(np.float64).reshape(shape) for _ in range(2))
+        a = adjoint64(r1, off, interp)
+        if abs(np.vdot(d1, a)) >= 0.5 * np.linalg.norm(d1) * np.linalg.norm(a) / np.sqrt(d1.size):
+            break
+    op = TraceSampling(off, interp=interp)
+    t = torch.empty(view, device=DEV)
+    _, rel = dottest(op, t, t, verbose=False, generator=torch.Generator().manual_seed(seed))
+    print("dottest relative error %.3e" % rel)
+    assert rel < 1e-5
+
+
+@pytest.mark.parametrize("interp", WIDE)
+@pytest.mark.parametrize("shape", [(2, 3, 5, 7), (1, 5, 67, 1), (1, 2, 33, 67)], ids=["2x3x5x7", "1x5x67x1", "1x2x33x67"])
+def test_autograd_backward_is_the_adjoint_and_the_adjoint_is_deterministic(shape, interp):
+    x, y, off, _, _, _, _, _ = _reference(shape, "random", interp)
+    op = TraceSampling(off, interp=interp)
+    view = _tensor_shape(shape)
+    xd, yd = x.view(view).to(DEV).requires_grad_(True), y.view(view).to(DEV)
+    op.forward(xd).backward(yd)
+    first = op.adjoint(yd)
+    assert torch.equal(xd.grad, first)                                  # bit for bit
+    assert torch.equal(op.adjoint(yd), first)                           # no atomics: two runs agree bit for bit
+    yg = yd.clone().requires_grad_(True)
+    op.adjoint(yg).backward(xd.detach())
+    assert torch.equal(yg.grad, op.forward(xd.detach()))
+
+
+def test_entry_points_refuse_bad_arguments():
+    """Each returns an error and launches nothing: the output keeps its fill."""
+    L = _lib.load()
+    t = torch.full((160,), 5.0, device=DEV)
+    src, off, out, w = t[:16], t[16:32], t[32:48], t[48:]
+    p, st = _lib.ptr, _lib.stream()
+    for fn in (L.dpi_trace_resample_fwd, L.dpi_trace_resample_adj):
+        assert fn(None, p(w), p(off), 4, 1, 2, 2, 2, p(out), st) != 0
+        assert fn(p(src), None, p(off), 4, 1, 2, 2, 2, p(out), st) != 0
+        assert fn(p(src), p(w), None, 4, 1, 2, 2, 2, p(out), st) != 0
+        assert fn(p(src), p(w), p(off), 4, 1, 2, 2, 2, None, st) != 0
+        assert fn(p(src), p(w), p(off), 4, 1, 2, 2, 2, p(src), st) != 0           # in == out
+        for K in (3, 16, 0, -2, 1):
+            assert fn(p(src), p(w), p(off), K, 1, 2, 2, 2, p(out), st) != 0
+        assert fn(p(src), p(w), p(off), 4, 1, 0, 2, 2, p(out), st) != 0           # T = 0
+        assert fn(p(src), p(w), p(off), 4, 0, 2, 2, 2, p(out), st) != 0
+        assert fn(p(src), p(w), p(off), 4, 1, 2, -1, 2, p(out), st) != 0
+        assert fn(p(src), p(w), p(off), 4, 1, 2, 2, 0, p(out), st) != 0
+        assert b"trace_resample" in L.dpi_last_error()
+    torch.cuda.synchronize()
+    assert bool((t == 5.0).all())
+
+
+def test_operator_refuses_a_foreign_grid_on_the_device():
+    op = TraceSampling(offsets_for("random", 5, 7), interp="sinc8")
+    with pytest.raises(ValueError, match="5 x 7"):
+        op.forward(torch.zeros(1, 2, 3, 7, 5, device=DEV))
+    with pytest.raises(ValueError, match="batch"):
+        op.adjoint(torch.zeros(2, 2, 3, 5, 7, device=DEV))
+
+
+# ---------------------------------------------------------------- the loop --------------------------------------------------------
+SHAPE = (16, 8, 8)
+EPOCHS = 20
+
+
+def _offsets(kind):
+    if kind is None:
+        return None
+    if kind == "zero":
+        return np.zeros(SHAPE[1:] + (2,), dtype=np.float32)
+    return np.random.RandomState(11).uniform(-0.5, 0.5, SHAPE[1:] + (2,)).astype(np.float32)
+
+
+def _run(tmp_path, mode, kind, interp=None, extra=()):
+    """The tiny 3-D multiunet of tests/test_gpu_trace_sampling.py (filters 4 8, skip 4, 8 input channels) on a 16 x 8 x 8 patch of the
+    off-grid stand-in, half the traces missing."""
+    from deep_prior_interpolation_amd.main import Interpolator
+    from deep_prior_interpolation_amd.parameter import parse_arguments
+    off = _offsets(kind)
+    a = parse_arguments(["--imgdir", "x", "--datadim", "3d", "--filters", "4", "8", "--skip", "4", "--inputdepth", "8", "--upsample", "linear",
+                         "--gain", "40", "--epochs", str(EPOCHS), "--gpu", "0"] + ([] if off is None else ["--trace_offsets", "off.npy"])
+                        + ([] if interp is None else ["--trace_interp", interp]) + list(extra))
+    truth = np.zeros(SHAPE[1:] + (2,), dtype=np.float32) if off is None else off
+    vol = u.hyperbolic_traces(SHAPE, truth, seed=3)[..., None].astype(np.float64) * a.gain
+    mask = np.broadcast_to(u.random_trace_mask(SHAPE, 0.5, seed=4)[..., None], vol.shape).astype(np.float64)
+    out = tmp_path / ("%s_%s_%s" % (mode, kind, interp))
+    os.makedirs(out)
+    data = {"image": vol, "mask": mask, "name": "0"}
+    if off is not None:
+        data["offsets"] = off
+    T = Interpolator(a, str(out))
+    T.load_data(data)
+    T.begin_patch(0)
+    T.build_model()
+    T.build_input()
+    T.optimize(verbose=False, mode=mode, check_every=4)
+    T.save_result()
+    return T, np.load(out / "0_run.npy", allow_pickle=True).item()
+
+
+def _history(T):
+    h = T.history
+    return [np.array(c) for c in (h.loss, h.snr, h.pcorr, h.lr)]
+
+
+@pytest.mark.parametrize("mode", ["eager", "graph"])
+def test_a_file_of_zeros_reproduces_the_run_without_either_flag(tmp_path, mode):
+    T0, run0 = _run(tmp_path, mode, None)
+    T1, run1 = _run(tmp_path, mode, "zero", "sinc8")
+    assert T0._sampling_op is None and T1._sampling_op.interp == "sinc8" and len(T1.history.loss) == EPOCHS
+    for a, b in zip(_history(T0), _history(T1)):
+        np.testing.assert_array_equal(a, b)                               # bit for bit
+    np.testing.assert_array_equal(T0.out_best, T1.out_best)
+    assert "trace_interp" not in run0 and "trace_offsets" not in run0 and run1["trace_interp"] == "sinc8" and not run1["trace_offsets"].any()
+
+
+@pytest.mark.parametrize("interp", WIDE)
+def test_random_offsets_eager_and_graph_and_what_is_saved(tmp_path, interp):
+    """Eager against graph (loss, snr and pcorr rtol 1e-12, lr rtol 1e-7, the selected output equal); the run file names the kind and its
+    `output` is the grid tensor."""
+    res = {}
+    for mode in ("eager", "graph"):
+        T, run = _run(tmp_path, mode, "random", interp)
+        assert len(T.history.loss) == EPOCHS and np.isfinite(T.history.loss).all()
+        res[mode] = (_history(T), T.out_best.copy())
+    for k in (0, 1, 2):
+        np.testing.assert_allclose(res["graph"][0][k], res["eager"][0][k], rtol=1e-12)
+    np.testing.assert_allclose(res["graph"][0][3], res["eager"][0][3], rtol=1e-7)
+    np.testing.assert_array_equal(res["graph"][1], res["eager"][1])
+    # T is the graph run
+    assert run["trace_interp"] == interp and T._sampling_op.interp == interp
+    np.testing.assert_array_equal(run["output"], T.out_best)
+    grid = T._out_best_dev.detach().float().reshape(T.img_.shape)
+    sampled = T.data_forward(grid).cpu().numpy()[0, 0]
+    grid = grid.cpu().numpy()[0, 0]
+    np.testing.assert_array_equal(np.squeeze(T.out_best), grid)           # what is kept is the grid tensor
+    assert (sampled != grid).any()
+
+
+def test_the_default_is_the_bilinear_operator(tmp_path):
+    """--trace_offsets alone and with --trace_interp linear spelled out: the same run bit for bit, through the bilinear entry points."""
+    T0, run0 = _run(tmp_path, "eager", "random")
+    T1, run1 = _run(tmp_path, "eager", "random", "linear")
+    assert T0._sampling_op.interp == T1._sampling_op.interp == "linear" and T0._sampling_op.weights is None
+    for a, b in zip(_history(T0), _history(T1)):
+        np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(T0.out_best, T1.out_best)
+    assert run0["trace_interp"] == run1["trace_interp"] == "linear"
+
+
+@pytest.mark.parametrize("mode", ["eager", "graph"])
+@pytest.mark.parametrize("interp", WIDE)
+def test_holdout_misfit_is_that_of_the_sampled_prediction(tmp_path, interp, mode):
+    """val_loss at best_iter, recomputed on the host from out_best through the float64 R of the kind: mean |R out - img| over the held-out
+    samples.  Bound: the 1e-6 relative error the loss pass is held to (tests/test_gpu_holdout.py) plus R's fp32 tolerance on every sample.
+    Through the bilinear R the same numbers do not come out: more than 10 tolerances away."""
+    T, run = _run(tmp_path, mode, "random", interp, ("--holdout", "0.2"))
+    assert run["holdout"] is not None and run["best_iter"] == T.best_iter and run["trace_interp"] == interp
+    off = np.moveaxis(run["trace_offsets"], -1, 0)                         # (2, X, Y), zero at unknown traces
+    held = run["holdout"][0, :, :, 0] > 0
+    assert held.sum() > 0 and np.all(off[:, held].any(axis=0))             # held-out traces keep their offsets
+    out = np.squeeze(T.out_best).astype(np.float64)[None]                  # (C, T, X, Y)
+    img = T.img[..., 0].astype(np.float32).astype(np.float64)
+    mh = (T.mask[..., 0] != 0) & held[None]
+
+    def misfit(pred):
+        e = (pred - img)[mh]
+        return (np.square(e) if T.loss_kind == "mse" else np.abs(e)).mean(), np.abs(e).max()
+
+    val, emax = misfit(forward64(out, off, interp)[0])
+    got = T.history.val_loss[T.best_iter]
+    tol = 1e-6 * val + forward_tolerance(interp_weights(off, interp), out) * (2 * emax if T.loss_kind == "mse" else 1.0)
+    print("val_loss %.9e, host %.9e, |diff| / tol = %.3f" % (got, val, abs(got - val) / tol))
+    assert abs(got - val) <= tol
+    other, _ = misfit(lin.forward64(out, off)[0])
+    print("through the bilinear R: %.9e, %.1f tolerances away" % (other, abs(other - got) / tol))
+    assert abs(other - got) > 10 * tol

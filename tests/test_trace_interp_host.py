@@ -1,0 +1,286 @@
+"""--trace_interp without a GPU: the library's weight builder against the float64 restatement of tests/trace_interp_cases.py, the properties
+of the three kernels, what they buy on plane waves and on the off-grid stand-in, the flag, checkpoints, the operator's refusals, the ABI
+table, and the weight builder as a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+from argparse import Namespace
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+from trace_interp_cases import (KINDS, OFFSET_KINDS, SHAPE_IDS, SHAPES, TAPS, adjoint64, dense_matrix, forward64, offsets_for, plane_wave_error,
+                                snr_db, tap_indices, weights64)
+
+from deep_prior_interpolation_amd import _lib, utils as u
+from deep_prior_interpolation_amd.operators import INTERP_TAPS, TraceSampling, interp_weights
+from deep_prior_interpolation_amd.parameter import net_args_are_same, parse_arguments
+
+HOST_SHAPES = [s for s in SHAPES if s[1] < 1000]          # the long-t case says nothing new about weights or the restatement
+HOST_IDS = [i for s, i in zip(SHAPES, SHAPE_IDS) if s[1] < 1000]
+U23, U24 = 2.0 ** -23, 2.0 ** -24
+
+
+# ---------------------------------------------------------------- the weight table -------------------------------------------------
+def test_names_and_tap_counts():
+    assert INTERP_TAPS == TAPS == {"linear": 2, "cubic": 4, "sinc8": 8} and list(INTERP_TAPS) == KINDS
+    L = _lib.load()
+    assert [L.dpi_trace_interp_taps(k) for k in (0, 1, 2)] == [2, 4, 8]
+    assert L.dpi_trace_interp_taps(3) == -1 and L.dpi_trace_interp_taps(-1) == -1
+
+
+@pytest.mark.parametrize("interp", KINDS)
+@pytest.mark.parametrize("kind", OFFSET_KINDS)
+@pytest.mark.parametrize("shape", HOST_SHAPES, ids=HOST_IDS)
+def test_library_table_against_float64(shape, kind, interp):
+    """Within 2^-23 absolute (one rounding of a weight of at most ~1 is 2^-24); sums to 1 within 4e-16 in float64 and K * 2^-24 in the table;
+    d = 0 is an exact unit tap."""
+    _, _, X, Y = shape
+    K = TAPS[interp]
+    off = offsets_for(kind, X, Y, seed=5)
+    w = interp_weights(off, interp)
+    ref = weights64(off, interp)
+    assert w.dtype == np.float32 and w.shape == ref.shape == (2, K, X, Y)
+    err = np.abs(w.astype(np.float64) - ref).max()
+    print("table error %.3e" % err)
+    assert err <= U23
+    total = np.asarray(ref, dtype=np.longdouble).sum(axis=1)          # what the float64 weights sum to, without the roundings of a float64 sum
+    print("float64 weights sum to 1 within %.3e" % float(np.abs(total - 1).max()))
+    assert float(np.abs(total - 1).max()) <= 4e-16
+    assert np.abs(w.astype(np.float64).sum(axis=1) - 1.0).max() <= K * U24
+    unit = (np.arange(K) == K // 2 - 1).astype(np.float32).reshape(1, K, 1, 1)
+    zero = np.broadcast_to((off == 0)[:, None], w.shape)
+    assert np.array_equal(w[zero], np.broadcast_to(unit, w.shape)[zero])
+    assert np.array_equal(ref[zero], np.broadcast_to(unit, w.shape)[zero].astype(np.float64))
+
+
+def test_linear_table_is_the_bilinear_weights():
+    off = offsets_for("random", 5, 7, seed=3)
+    w = interp_weights(off, "linear")
+    pos = off >= 0
+    assert np.array_equal(w[:, 0], np.where(pos, np.float32(1) - off, -off)) and np.array_equal(w[:, 1], np.where(pos, off, np.float32(1) + off))
+
+
+def test_cubic_at_half_a_cell_is_exact():
+    for d, expect in ((0.5, [-1 / 16, 9 / 16, 9 / 16, -1 / 16]), (-0.5, [-1 / 16, 9 / 16, 9 / 16, -1 / 16])):
+        off = np.full((2, 1, 1), d, dtype=np.float32)
+        assert interp_weights(off, "cubic")[0, :, 0, 0].tolist() == expect
+        assert weights64(off, "cubic")[0, :, 0, 0].tolist() == expect
+
+
+@pytest.mark.parametrize("term", ["x2", "xy", "y2"])
+def test_cubic_reproduces_quadratics_on_the_interior(term):
+    """Keys' a = -1/2 kernel reproduces polynomials up to degree 2 where no tap clamps: rows / columns 2 .. 9 of a 12 x 12 grid."""
+    n = 12
+    off = offsets_for("random", n, n, seed=7)
+    gx, gy = np.meshgrid(np.arange(n, dtype=np.float64), np.arange(n, dtype=np.float64), indexing="ij")
+    f = {"x2": lambda x, y: x * x, "xy": lambda x, y: x * y, "y2": lambda x, y: y * y}[term]
+    got = forward64(f(gx, gy)[None, None], off, "cubic")[0, 0]
+    want = f(gx + off[0].astype(np.float64), gy + off[1].astype(np.float64))
+    assert np.abs(got - want)[2:-2, 2:-2].max() <= 1e-12
+
+
+@pytest.mark.parametrize("interp", KINDS)
+def test_weights_mirror_with_the_sign_of_the_offset(interp):
+    """w(d)[k] == w(-d)[K - 1 - k]: exactly in the library's table, to rounding in the restatement (its sinc8 sum runs the other way)."""
+    d = np.random.RandomState(0).uniform(0.0, 0.5, (2, 8, 9)).astype(np.float32)
+    d[0, 0, :3] = [0.5, 0.25, 2.0 ** -20]
+    a, b = interp_weights(d, interp), interp_weights(-d, interp)
+    assert np.array_equal(a, b[:, ::-1])
+    np.testing.assert_allclose(weights64(d, interp), weights64(-d, interp)[:, ::-1], rtol=0, atol=1e-15)
+
+
+@pytest.mark.parametrize("interp", KINDS)
+@pytest.mark.parametrize("kind", OFFSET_KINDS)
+@pytest.mark.parametrize("shape", HOST_SHAPES, ids=HOST_IDS)
+def test_restatement_passes_its_own_dot_test(shape, kind, interp):
+    rng = np.random.RandomState(1)
+    off = offsets_for(kind, shape[2], shape[3], seed=2)
+    d, r = rng.standard_normal(shape), rng.standard_normal(shape)
+    lhs, rhs = np.vdot(forward64(d, off, interp), r), np.vdot(d, adjoint64(r, off, interp))
+    assert abs(lhs - rhs) <= 1e-12 * max(abs(lhs), np.linalg.norm(d) * np.linalg.norm(r))
+    if shape[2] * shape[3] <= 128:                                    # the dense matrix is the same operator
+        M = dense_matrix(off, interp)
+        flat = d.reshape(-1, shape[2] * shape[3])
+        np.testing.assert_allclose((flat @ M.T).reshape(shape), forward64(d, off, interp), rtol=0, atol=1e-12 * np.abs(d).max() * 8)
+        np.testing.assert_allclose((flat @ M).reshape(shape), adjoint64(d, off, interp), rtol=0, atol=1e-12 * np.abs(d).max() * 8)
+
+
+def test_linear_restatement_is_the_bilinear_one():
+    import trace_sampling_cases as lin
+    x = np.random.RandomState(4).standard_normal((2, 3, 5, 7))
+    for kind in OFFSET_KINDS:
+        off = offsets_for(kind, 5, 7, seed=6)
+        np.testing.assert_allclose(forward64(x, off, "linear"), lin.forward64(x, off), rtol=0, atol=1e-15)
+        np.testing.assert_allclose(adjoint64(x, off, "linear"), lin.adjoint64(x, off), rtol=0, atol=1e-15)
+    i0, i1, _, _ = lin.axis_taps(np.arange(5)[:, None], offsets_for("random", 5, 7, seed=6)[0], 5)
+    tx, _ = tap_indices(offsets_for("random", 5, 7, seed=6), 2)
+    assert np.array_equal(tx[0], i0) and np.array_equal(tx[1], i1)
+
+
+@pytest.mark.parametrize("interp", KINDS)
+@pytest.mark.parametrize("shape", HOST_SHAPES, ids=HOST_IDS)
+def test_zero_offsets_give_the_identity(shape, interp):
+    x = np.random.RandomState(3).standard_normal(shape)
+    off = offsets_for("zero", shape[2], shape[3])
+    assert np.array_equal(forward64(x, off, interp), x) and np.array_equal(adjoint64(x, off, interp), x)
+
+
+# ---------------------------------------------------------------- what the kernels buy ---------------------------------------------
+def test_plane_wave_error_at_half_nyquist_is_ordered():
+    """Worst |R e^{ikx} - e^{ik(x + d)}| over d at k = 0.5 Nyquist: 0.0003 / 0.116 / 0.293 for sinc8 / cubic / linear."""
+    e = {k: plane_wave_error(k, 0.5) for k in KINDS}
+    print(e)
+    assert e["sinc8"] < 0.01 < e["cubic"] < 0.2 < e["linear"]
+
+
+def test_modelling_floor_on_the_stand_in():
+    """snr(R(truth), traces) at 48x32x32 through the LIBRARY's tables, offsets RandomState(2).uniform(-0.5, 0.5) as tools/offgrid_quality.py
+    draws them: 13.27 / 17.04 / 19.67 dB for linear / cubic / sinc8.  cubic >= linear + 3 dB, sinc8 >= cubic + 2 dB."""
+    shape = (48, 32, 32)
+    off = np.random.RandomState(2).uniform(-0.5, 0.5, shape[1:] + (2,)).astype(np.float32)
+    truth = u.hyperbolic_volume(shape, 0, background=0).astype(np.float64)
+    traces = u.hyperbolic_traces(shape, off, 0).astype(np.float64)
+    o = np.moveaxis(off, -1, 0)
+    floor = {k: snr_db(traces, forward64(truth[None], o, k, w=interp_weights(o, k))[0]) for k in KINDS}
+    print(floor)
+    assert floor["cubic"] >= floor["linear"] + 3.0 and floor["sinc8"] >= floor["cubic"] + 2.0
+    assert abs(floor["linear"] - 13.27) < 0.05 and abs(floor["cubic"] - 17.04) < 0.05 and abs(floor["sinc8"] - 19.67) < 0.05
+
+
+# ---------------------------------------------------------------- flag, checkpoints, operator --------------------------------------
+BASE3 = ["--imgdir", "x", "--datadim", "3d"]
+OFFS = ["--trace_offsets", "off.npy"]
+
+
+def test_flag_parses_and_needs_trace_offsets():
+    assert parse_arguments(BASE3).trace_interp == "linear"
+    assert parse_arguments(BASE3 + OFFS).trace_interp == "linear"
+    for name in KINDS:
+        assert parse_arguments(BASE3 + OFFS + ["--trace_interp", name]).trace_interp == name
+        assert parse_arguments(["--imgdir", "x", "--datadim", "2d"] + OFFS + ["--trace_interp", name, "--holdout", "0.2"]).trace_interp == name
+    assert parse_arguments(BASE3 + ["--trace_interp", "linear"]).trace_interp == "linear"          # the default, spelled out
+    for name in ("cubic", "sinc8"):
+        with pytest.raises(ValueError, match="--trace_interp"):
+            parse_arguments(BASE3 + ["--trace_interp", name])
+    with pytest.raises(SystemExit):
+        parse_arguments(BASE3 + OFFS + ["--trace_interp", "sinc6"])
+
+
+@pytest.mark.parametrize("argv", [
+    ["--imgdir", "x", "--datadim", "2.5d", "--imgchannel", "3"] + OFFS,
+    ["--imgdir", "x", "--datadim", "2.5d", "--slice", "tx", "--imgchannel", "5", "--avo_theta", "0", "10", "20", "30", "40"] + OFFS,
+    BASE3 + OFFS + ["--out_ema", "0.9"],
+    BASE3 + OFFS + ["--optimizer", "sgld"],
+], ids=["2.5d", "avo_theta", "out_ema", "sgld"])
+def test_what_trace_offsets_refuses_stays_refused(argv):
+    with pytest.raises(ValueError, match="--trace_offsets"):
+        parse_arguments(argv + ["--trace_interp", "sinc8"])
+
+
+def test_main_pocs_still_refuses():
+    from deep_prior_interpolation_amd.main_pocs import Interpolator
+    with pytest.raises(ValueError, match="--trace_offsets"):
+        Interpolator(parse_arguments(BASE3 + OFFS + ["--trace_interp", "cubic"]), "/tmp", device="cpu")
+
+
+def test_checkpoints():
+    lin, cub, snc = (parse_arguments(BASE3 + OFFS + ["--trace_interp", k]) for k in KINDS)
+    old = Namespace(**{k: v for k, v in vars(lin).items() if k != "trace_interp"})              # an args.txt from before the flag
+    assert not hasattr(old, "trace_interp")
+    assert net_args_are_same(lin, old) and net_args_are_same(old, lin)                         # a missing key reads as linear
+    assert net_args_are_same(cub, parse_arguments(BASE3 + OFFS + ["--trace_interp", "cubic"]))
+    for a, b in ((cub, old), (old, cub), (cub, lin), (lin, cub), (snc, cub), (cub, snc)):
+        assert not net_args_are_same(a, b)
+    none = parse_arguments(BASE3)
+    assert net_args_are_same(none, Namespace(**{k: v for k, v in vars(none).items() if k not in ("trace_interp", "trace_offsets")}))
+
+
+def test_operator_refusals_and_attributes():
+    off = offsets_for("random", 5, 7)
+    assert TraceSampling(off).interp == "linear" and TraceSampling(off).weights is None
+    for name in ("cubic", "sinc8"):
+        op = TraceSampling(off, interp=name)
+        assert op.interp == name and op.offsets.dtype == torch.float32 and tuple(op.offsets.shape) == (2, 5, 7)
+        assert tuple(op.weights.shape) == (2, TAPS[name], 5, 7) and np.array_equal(op.weights.numpy(), interp_weights(off, name))
+        with pytest.raises(ValueError, match="5 x 7"):                  # a foreign grid, refused from the shapes alone
+            op._apply(torch.zeros(1, 2, 3, 7, 5), False)
+        with pytest.raises(ValueError, match="5 x 7"):
+            op._apply(torch.zeros(1, 2, 3, 5), True)
+        with pytest.raises(ValueError, match="batch"):
+            op._apply(torch.zeros(2, 2, 3, 5, 7), False)
+    for bad in ("sinc6", "nearest", None, 2):
+        with pytest.raises(ValueError, match="interpolation"):
+            TraceSampling(off, interp=bad)
+        with pytest.raises(ValueError, match="interpolation"):
+            interp_weights(off, bad)
+    worse = off.copy()
+    worse[0, 1, 1] = 0.6
+    with pytest.raises(ValueError, match=r"\[-0.5, 0.5\]"):
+        TraceSampling(worse, interp="cubic")
+
+
+# ---------------------------------------------------------------- ABI --------------------------------------------------------------
+NEW = ("dpi_trace_interp_taps", "dpi_trace_interp_weights", "dpi_trace_resample_fwd", "dpi_trace_resample_adj")
+
+
+def test_abi_table_header_exports_and_makefile_name_the_entry_points():
+    assert _lib.ABI_VERSION == 406
+    h = open(os.path.join(ROOT, "include", "dpi_hip.h")).read()
+    for line in ("int dpi_trace_interp_taps(int kind);",
+                 "int dpi_trace_interp_weights(const float* off, int kind, int X, int Y, float* w);",
+                 "int dpi_trace_resample_fwd(const float* x, const float* w, const float* off, int K, int C, int T, int X, int Y, float* y, "
+                 "void* stream);",
+                 "int dpi_trace_resample_adj(const float* y, const float* w, const float* off, int K, int C, int T, int X, int Y, float* x, "
+                 "void* stream);"):
+        assert line in h
+    I, P = C.c_int, C.c_void_p
+    assert _lib.SIGNATURES["dpi_trace_interp_taps"] == (I, [I])
+    assert _lib.SIGNATURES["dpi_trace_interp_weights"] == (I, [P, I, I, I, P])
+    for name in NEW[2:]:
+        assert _lib.SIGNATURES[name] == (I, [P, P, P, I, I, I, I, I, P, P])
+    mk = open(os.path.join(ROOT, "deep_prior_interpolation_amd", "csrc", "Makefile")).read()
+    assert "trace_resample.hip" in mk and "trace_interp.cpp" in mk and "trace_sample.hip" in mk
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    for name in NEW + ("dpi_trace_sample_fwd", "dpi_trace_sample_adj"):
+        assert (" T " + name + "\n") in exported
+    assert _lib.load().dpi_version() == 406
+
+
+def test_weight_builder_refusals():
+    L = _lib.load()
+    off = np.zeros((2, 3, 4), dtype=np.float32)
+    w = np.full((2, 8, 3, 4), 5.0, dtype=np.float32)
+    po, pw = off.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p)
+    assert L.dpi_trace_interp_weights(None, 1, 3, 4, pw) != 0
+    assert L.dpi_trace_interp_weights(po, 1, 3, 4, None) != 0
+    assert b"trace_interp_weights" in L.dpi_last_error()
+    for kind, X, Y in ((3, 3, 4), (-1, 3, 4), (1, 0, 4), (1, 3, 0), (2, -3, 4)):
+        assert L.dpi_trace_interp_weights(po, kind, X, Y, pw) != 0
+    assert bool((w == 5.0).all())
+    assert L.dpi_trace_interp_weights(po, 2, 3, 4, pw) == 0 and w.sum() == 24.0
+
+
+# ---------------------------------------------------------------- the weight builder under sanitizers ------------------------------
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs the ROCm compiler")
+def test_weight_builder_under_asan_and_ubsan(tmp_path):
+    """csrc/trace_interp.cpp is plain C++: compiled with tests/host_weights/main.cpp under the address and undefined-behaviour sanitizers
+    into a program of its own and run on the CPU, over the (X, Y) of the host shapes and the four offset kinds, with exactly-sized heap
+    buffers.  The sanitizers instrument host code only: nothing here is compiled for, or run on, a device."""
+    exe = str(tmp_path / "host_weights")
+    flags = "-x c++ -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
+    subprocess.check_call([HIPCC] + flags.split() + [os.path.join(ROOT, "deep_prior_interpolation_amd", "csrc", "trace_interp.cpp"),
+                           os.path.join(ROOT, "tests", "host_weights", "main.cpp"), "-o", exe], timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert " 0 failures" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
