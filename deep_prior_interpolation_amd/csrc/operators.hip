@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void diff_axis_kernel(const float* __restrict_
       else if (stencil == 2) r = 0.5f * ((i - 1 >= 1 && i - 1 <= n - 2) ? dn : 0.f) - 0.5f * ((i + 1 >= 1 && i + 1 <= n - 2) ? up : 0.f);
       else r = ((i - 1 >= 1 && i - 1 <= n - 2) ? dn : 0.f) - 2.f * ((i >= 1 && i <= n - 2) ? c : 0.f) + ((i + 1 >= 1 && i + 1 <= n - 2) ? up : 0.f);
     }
-    y[idx] = r / scale;        // a division, like the reference (bit parity for spacings that are not powers of two)
+    y[idx] = r / scale;        // a division, like the reference (bit parity of stencils 0-2 for spacings that are not powers of two)
   }
 }
 

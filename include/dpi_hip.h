@@ -352,7 +352,10 @@ int dpi_pconv_mask_bwd(const float* dxm, const float* x, const float* m, int Cin
 /* ---------------------------------------------------------------- plain 2-D UNet extras ----------
  * Replaces nn.MaxPool2d(2, 2) (unet.py:42) and nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1) (unet.py:59) with
  * their backward passes.  x: [C][H][W]; pooled / transposed outputs are [C][H/2][W/2] and [Cout][2H][2W];
- * deconv weight layout is torch's [Cin][Cout][4][4]. */
+ * deconv weight layout is torch's [Cin][Cout][4][4].  bias [Cout] or NULL; H, W >= 1 for the transposed convolution, >= 2 for the pool.
+ * The pool takes the first maximum of a window in (kh, kw) scan order, like aten: a later tap replaces the running maximum only if it
+ * is greater, so of equal taps (0.0 and -0.0 included) the first is returned and receives dy, and a NaN is never selected unless it is
+ * tap (0, 0).  dpi_maxpool2x2_bwd writes all of dx: 0 at the other taps and in the trailing row / column of an odd H / W. */
 int dpi_maxpool2x2_fwd(const float* x, int C, int H, int W, float* y, void* stream);
 int dpi_maxpool2x2_bwd(const float* dy, const float* x, int C, int H, int W, float* dx, void* stream);
 int dpi_deconv4x4s2_fwd(const float* x, const float* w, const float* bias, int Cin, int Cout, int H, int W,
@@ -542,7 +545,10 @@ int dpi_overlap_finalize_weighted(const float* acc, int K, int D, int H, int W, 
  *
  * dpi_diff_axis replaces utils/processing.py:139-181 first_derivative (stencil 0 forward, 1 backward, 2 centered) and
  * second_derivative (stencil 3) along the middle axis of a contiguous [outer][n][inner] view, and with stencil 0, spacing 1 on the
- * H axis of BCHW it is operators/derivative.py:8-21 VerticalGrad.forward / .adjoint.   x != y. */
+ * H axis of BCHW it is operators/derivative.py:8-21 VerticalGrad.forward / .adjoint.   x != y.
+ * The differences are followed by ONE fp32 division by the spacing, like the reference, so the three first derivatives are the reference's
+ * bits.  The second derivative divides by the fp32 product spacing * spacing of the fp32 argument, where the reference rounds the double
+ * spacing ** 2 once: the two divisors can be one ulp apart (0.7: they are), the quotients two. */
 int dpi_diff_axis(const float* x, size_t outer, int n, size_t inner, int stencil, float spacing, int adjoint, float* y,
                   void* stream);
 /* Replaces utils/slopes.py:51-105 directional_laplacian / Hale2D.forward on [N][H][W] planes with coefficient planes
@@ -550,7 +556,11 @@ int dpi_diff_axis(const float* x, size_t outer, int n, size_t inner, int stencil
 int dpi_hale2d(const float* x, const float* a, const float* b, const float* c, size_t N, int H, int W, int adjoint, float* y,
                void* stream);
 /* Replaces utils/slopes.py:19-22 (forward-difference gradients and their products) and :35-46 (eigen-analysis: dip angle phi
- * with NaN -> 0, anisotropy 1 - l2/l1); the Gaussian smoothing in between (:25-32) is dpi_fir_axis0 along H and W. */
+ * with NaN -> 0, anisotropy 1 - l2/l1); the Gaussian smoothing in between (:25-32) is dpi_fir_axis0 along H and W.
+ * dpi_dips evaluates t1 = (gvv + ghh) / 2, t2 = sqrt((gvv - ghh)^2 + 4 gvh^2) / 2, l1 = t1 + t2, l2 = t1 - t2 in fp32, one rounding per
+ * operation, and leaves the special cases as IEEE gives them: with gvh = 0 the ratio (l1 - gvv) / gvh is 0 / 0 where l1 == gvv (a
+ * diagonal tensor with gvv >= ghh, e.g. (3, 0, 1)), which gives phi = 0, and +-inf otherwise ((1, 0, 3): phi = +pi/2); the zero tensor has
+ * phi = 0 and the anisotropy NaN. */
 int dpi_structure_tensor(const float* x, size_t N, int H, int W, float dv, float dh, float* gvv, float* gvh, float* ghh,
                          void* stream);
 int dpi_dips(const float* gvv, const float* gvh, const float* ghh, size_t n, float* phi, float* anisotropy, void* stream);
@@ -625,7 +635,11 @@ int dpi_trace_resample_adj(const float* y, const float* w, const float* off, int
 /* ---------------------------------------------------------------- POCS regulariser --------------
  * Replaces utils/pocs.py:5-19 (threshold / compute_threshold: out = max(x) * scale with scale = perc/100, kept on the device;
  * y = x * ((x > th) + (x < -th)) on the real view of the spectrum) and :80-84 (y = weighted_data + weighted_mask * x).
- * The transform between them (reference: torch.rfft / irfft, main_pocs.py:156-157) is the rocFFT library call. */
+ * The transform between them (reference: torch.rfft / irfft, main_pocs.py:156-157) is the rocFFT library call.
+ * dpi_scaled_max: ws = dpi_max_ws_floats(n) floats, out = one float = fp32(max x) * scale.  The maximum is taken with fmaxf, which ignores
+ * a NaN where torch.max would return it; a tensor of NaN only gives -inf * scale.  dpi_threshold reads *thresh on the device; the two
+ * flags are added as floats like the reference's, so the inequalities are strict (x == th and x == -th give 0) and a negative th, for
+ * which both hold on |x| < -th, gives 2 x there. */
 size_t dpi_max_ws_floats(size_t n);
 int dpi_scaled_max(const float* x, size_t n, float scale, float* ws, float* out, void* stream);
 int dpi_threshold(const float* x, size_t n, const float* thresh, float* y, void* stream);
