@@ -3,7 +3,8 @@
 `get_net(args, outchannel)` consumes the same Namespace fields (datadim, net, inputdepth, filters, skip,
 upsample, activation, last_activation, dropout) and returns an nn.Module whose state_dict keys equal the
 reference's, built from HIP-backed leaf modules.  `build_net` is what the Interpolator calls: get_net plus `--datadim 3d --net part`,
-a route of get_net that the host suite pins as refused.
+a route of get_net that the host suite pins as refused, and `--datadim 3d --net unet`, which get_net (like the reference's) lets fall through to
+MulResUnet3D and build_net routes to UNet3D.
 """
 from .base import *            # noqa: F401,F403
 from .mulresunet import *      # noqa: F401,F403
@@ -11,7 +12,7 @@ from .skip import *            # noqa: F401,F403
 from .unet import *            # noqa: F401,F403
 from .attention import *       # noqa: F401,F403
 from .partial_unet import *    # noqa: F401,F403
-from .unet import UNet
+from .unet import UNet, UNet3D
 from .attention import AttMulResUnet2D, AttMulResUnet3D
 from .mulresunet import MulResUnet, MulResUnet3D
 from .partial_unet import PartialUNet, PartialUNet3D
@@ -23,9 +24,13 @@ def _partial(cls, args, outchannel):
 
 
 def build_net(args, outchannel=1):
-    """What the Interpolator builds: get_net, and the one net that get_net's pinned routes keep from it — `--datadim 3d --net part`."""
+    """What the Interpolator builds: get_net, and the nets that get_net's pinned routes keep from it — `--datadim 3d --net part` and
+    `--datadim 3d --net unet` (get_net keeps the reference's fall-through to MulResUnet3D there: its drop-in contract)."""
     if getattr(args, "net", "multiunet") == "part" and args.datadim == "3d":
         return _partial(PartialUNet3D, args, outchannel)
+    if getattr(args, "net", "multiunet") == "unet" and args.datadim == "3d":
+        return UNet3D(num_input_channels=args.inputdepth, num_output_channels=outchannel, filters=args.filters, upsample_mode=args.upsample,
+                      need_bias=True, act_fun=args.activation, last_act_fun=args.last_activation, dropout=args.dropout)
     return get_net(args, outchannel)
 
 

@@ -89,6 +89,30 @@ class ConvTranspose2d(nn.ConvTranspose2d):
         return ops.conv_transpose4x4s2(x, self.weight, self.bias)
 
 
+class InstanceNorm3d(InstanceNorm2d):
+    """nn.InstanceNorm3d(C) with its defaults, as InstanceNorm2d: the BatchNorm kernels take (1, C, D, H, W) as they take (1, C, H, W)."""
+
+
+class MaxPool3d(nn.Module):
+    def __init__(self, kernel_size=2, stride=2):
+        super().__init__()
+        if kernel_size != 2 or stride != 2:
+            raise NotImplementedError("only MaxPool3d(2, 2)")
+
+    def forward(self, x):
+        return ops.max_pool2x2x2(x)
+
+
+class ConvTranspose3d(nn.ConvTranspose3d):
+    def __init__(self, in_f, out_f, kernel_size=4, stride=2, padding=1):
+        super().__init__(in_f, out_f, kernel_size, stride=stride, padding=padding)
+        if (kernel_size, stride, padding) != (4, 2, 1):
+            raise NotImplementedError("only ConvTranspose3d(k=4, stride=2, padding=1)")
+
+    def forward(self, x):
+        return ops.conv_transpose4x4x4s2(x, self.weight, self.bias)
+
+
 class LeakyReLU(nn.Module):
     """LeakyReLU(slope); slope=0 gives ReLU.  (Out of place; the reference's inplace=True is a memory detail.)"""
 

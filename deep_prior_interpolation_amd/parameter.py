@@ -37,8 +37,9 @@ _FLAGS = [
     (("--skip",), dict(nargs="+", type=int, required=False, default=[16, 32, 64, 128],
                        help="Number of channels for skip-connection")),
     (("--inputdepth",), dict(type=int, required=False, default=64, help="Depth of the input noise tensor")),
-    (("--upsample",), dict(type=str, required=False, default="nearest", choices=["nearest", "linear"],
-                           help="Network's upgoing deconvolution strategy")),
+    (("--upsample",), dict(type=str, required=False, default="nearest", choices=["nearest", "linear", "deconv"],
+                           help="Network's upgoing deconvolution strategy; deconv (ours on the command line) = transposed convolution "
+                                "(k=4, s=2, p=1), --net unet only")),
     (("--inittype",), dict(type=str, required=False, default="xavier",
                            choices=["xavier", "normal", "default", "kaiming", "orthogonal"],
                            help="Initialization strategy for the network weights")),
@@ -161,6 +162,9 @@ def postprocess(args: Namespace) -> Namespace:
     """Derived defaults of parameter.py:113-125."""
     if args.upsample == "linear":
         args.upsample = "trilinear" if args.datadim == "3d" else "bilinear"
+    if args.upsample == "deconv" and getattr(args, "net", "multiunet") not in ("unet", "load"):     # load: the saved args.txt decides
+        raise ValueError("--upsample deconv needs --net unet (2d, 2.5d or 3d), got --net %s: the other nets up-sample by interpolation "
+                         "and have no transposed convolution" % getattr(args, "net", "multiunet"))
     if args.patch_shape is None:
         args.patch_shape = [-1, -1] if args.datadim == "2d" else [-1, -1, -1]
     if args.patch_stride is None:

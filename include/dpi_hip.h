@@ -365,6 +365,34 @@ int dpi_deconv4x4s2_bwd_data(const float* dy, const float* w, int Cin, int Cout,
 int dpi_deconv4x4s2_bwd_weight(const float* x, const float* dy, int Cin, int Cout, int H, int W, float* dw,
                                void* stream);
 
+/* ---------------------------------------------------------------- plain 3-D UNet extras ----------
+ * nn.MaxPool3d(2, 2) and nn.ConvTranspose3d(Cin, Cout, 4, stride=2, padding=1) with their backward passes, for UNet3D (ours: the
+ * reference has no 3-D form of its plain UNet).  fp32 in every --precision mode.  x: [C][D][H][W]; pooled / transposed outputs are
+ * [C][D/2][H/2][W/2] (floor) and [Cout][2D][2H][2W]; deconv weight layout is torch's [Cin][Cout][4][4][4]; bias [Cout] or NULL.
+ * D, H, W >= 1 for the transposed convolution, >= 2 for the pool.  Tensors may be views at any element offset.
+ * Pool: y[c][od][oh][ow] = the first maximum of x[c][2od + kd][2oh + kh][2ow + kw] in (kd, kh, kw) scan order, like aten: a later tap
+ * replaces the running maximum only if it is greater, so of equal taps (0.0 and -0.0 included) the first is returned and receives dy,
+ * and a NaN is never selected unless it is tap (0, 0, 0).  dpi_maxpool2x2x2_bwd writes all of dx: 0 at the other taps and in the
+ * trailing plane / row / column of an odd D / H / W.
+ * Transposed convolution: y[co][od][oh][ow] = bias[co] + sum over ci and the taps with o = 2 i - 1 + k on every axis of
+ * x[ci][id][ih][iw] w[ci][co][kd][kh][kw] (at most 2 x 2 x 2 taps reach an output);  dx[ci][i] = sum over co and the 4 x 4 x 4 taps of
+ * dy[co][2 i - 1 + k] w[ci][co][k] (outputs outside the tensor add 0);  dw[ci][co][k] = sum over i of x[ci][i] dy[co][2 i - 1 + k].
+ * With Cin and Cout multiples of 16 the three run as GEMMs over the eight output-parity classes on v_mfma_f32_16x16x4_f32 (operands
+ * staged in LDS, fp32 accumulation); other channel counts take one-thread-per-output VALU kernels.  Either way the summation order is
+ * fixed and there are no atomics: two launches on the same data give the same bits.  ws of dpi_deconv4x4x4s2_bwd_weight:
+ * dpi_deconv4x4x4s2_bwd_weight_ws_floats floats (0 = bad geometry, never 0 otherwise).
+ * Refused with DPI_E_ARG before any launch: a NULL pointer (bias excepted), an output that is one of the inputs, a non-positive size,
+ * and a tensor of the call with more than 2^31 - 1 elements. */
+int dpi_maxpool2x2x2_fwd(const float* x, int C, int D, int H, int W, float* y, void* stream);
+int dpi_maxpool2x2x2_bwd(const float* dy, const float* x, int C, int D, int H, int W, float* dx, void* stream);
+int dpi_deconv4x4x4s2_fwd(const float* x, const float* w, const float* bias, int Cin, int Cout, int D, int H, int W,
+                          float* y, void* stream);
+int dpi_deconv4x4x4s2_bwd_data(const float* dy, const float* w, int Cin, int Cout, int D, int H, int W, float* dx,
+                               void* stream);
+size_t dpi_deconv4x4x4s2_bwd_weight_ws_floats(int Cin, int Cout, int D, int H, int W);
+int dpi_deconv4x4x4s2_bwd_weight(const float* x, const float* dy, int Cin, int Cout, int D, int H, int W, float* dw,
+                                 float* ws, void* stream);
+
 /* ---------------------------------------------------------------- loss + metrics ----------------
  * Replaces main.py:161-167: loss = mean(|out*m - img*m|) (kind 0, L1) or mean((.)^2) (kind 1, MSE)
  * over all n elements; dout = dloss/dout * grad_scale; plus the sums for snr/pcorr
