@@ -1,6 +1,7 @@
 // Masked L1/MSE loss with fused gradient and SNR/PCORR sums, the running average of the output (--out_ema), multi-tensor Adam, Philox input noise,
 // overlap-add patch reassembly.
 #include "common.h"
+#include "loop_rule.h"
 
 namespace {
 
@@ -492,126 +493,19 @@ __global__ __launch_bounds__(256) void overlap_finalize_weighted_kernel(const fl
 }
 
 // ---- device-resident loop control (one thread): history row, best-output flag, ReduceLROnPlateau, EarlyStopping ---------
-// state (double[8]): {iter, loss_min, plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved}
-__global__ void loop_control_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist,
-                                    int max_iters, float* __restrict__ step_lr, int* __restrict__ active, int* __restrict__ improved,
-                                    int use_plateau, double factor, double threshold, int patience, double min_lr, double lr_eps,
-                                    int es_patience, double es_min_delta) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  *improved = 0;
-  if (!*active) return;
-  const int it = (int)state[0];
-  const double loss = metrics[0];
-  const double lr = (double)step_lr[1];
-  if (it < max_iters) { hist[4 * it + 0] = loss; hist[4 * it + 1] = metrics[1]; hist[4 * it + 2] = metrics[2]; hist[4 * it + 3] = lr; }
-  if (it == 0 || loss <= state[1]) { state[1] = loss; *improved = 1; }                     // main.py:173-180
-  if (use_plateau) {                                                                        // torch ReduceLROnPlateau, mode min / rel
-    if (loss < state[2] * (1.0 - threshold)) { state[2] = loss; state[3] = 0.0; }
-    else state[3] += 1.0;
-    if (state[3] > (double)patience) {
-      const double nl = fmax(lr * factor, min_lr);
-      if (lr - nl > lr_eps) step_lr[1] = (float)nl;
-      state[3] = 0.0;
-    }
-  }
-  if (es_patience != 0) {                                                                   // utils/torch.py:216-275, percentage mode
-    if (state[6] == 0.0) { state[4] = loss; state[6] = 1.0; }
-    else if (loss != loss) *active = 0;                                                     // NaN loss stops immediately
-    else {
-      if (loss < state[4] - state[4] * es_min_delta / 100.0) { state[5] = 0.0; state[4] = loss; }
-      else state[5] += 1.0;
-      if (state[5] >= (double)es_patience) *active = 0;
-    }
-  }
-  state[0] = (double)(it + 1);
+// The rule, the state slots and the history rows of the three variants are those of loop_rule.h (dpi_loop_rule).
+__global__ void loop_control_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist, int max_iters,
+                                    float* __restrict__ step_lr, int* __restrict__ active, int* __restrict__ improved, dpi_loop_rules r) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) dpi_loop_rule(metrics, nullptr, false, state, hist, max_iters, step_lr, active, improved, r);
 }
-
-// The same with a held-out part (--holdout): metrics = the 11 doubles of dpi_masked_loss_holdout; history rows of six
-// {loss, snr, pcorr, lr, val_loss, val_snr}; out_best and early stopping follow val_loss, ReduceLROnPlateau the training loss.
-// state (double[10]): {iter, loss_min, plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved, val_min, best_iter}
-__global__ void loop_control_holdout_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist,
-                                            int max_iters, float* __restrict__ step_lr, int* __restrict__ active, int* __restrict__ improved,
-                                            int use_plateau, double factor, double threshold, int patience, double min_lr, double lr_eps,
-                                            int es_patience, double es_min_delta) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  *improved = 0;
-  if (!*active) return;
-  const int it = (int)state[0];
-  const double loss = metrics[0], val = metrics[8];
-  const double lr = (double)step_lr[1];
-  if (it < max_iters) {
-    double* row = hist + 6 * (size_t)it;
-    row[0] = loss; row[1] = metrics[1]; row[2] = metrics[2]; row[3] = lr; row[4] = val; row[5] = metrics[9];
-  }
-  if (it == 0 || loss <= state[1]) state[1] = loss;
-  if (it == 0 || val <= state[8]) { state[8] = val; state[9] = (double)it; *improved = 1; }
-  if (use_plateau) {
-    if (loss < state[2] * (1.0 - threshold)) { state[2] = loss; state[3] = 0.0; }
-    else state[3] += 1.0;
-    if (state[3] > (double)patience) {
-      const double nl = fmax(lr * factor, min_lr);
-      if (lr - nl > lr_eps) step_lr[1] = (float)nl;
-      state[3] = 0.0;
-    }
-  }
-  if (es_patience != 0) {
-    if (state[6] == 0.0) { state[4] = val; state[6] = 1.0; }
-    else if (val != val) *active = 0;
-    else {
-      if (val < state[4] - state[4] * es_min_delta / 100.0) { state[5] = 0.0; state[4] = val; }
-      else state[5] += 1.0;
-      if (state[5] >= (double)es_patience) *active = 0;
-    }
-  }
-  state[0] = (double)(it + 1);
+__global__ void loop_control_holdout_kernel(const double* __restrict__ metrics, double* __restrict__ state, double* __restrict__ hist, int max_iters,
+                                            float* __restrict__ step_lr, int* __restrict__ active, int* __restrict__ improved, dpi_loop_rules r) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) dpi_loop_rule(metrics, nullptr, true, state, hist, max_iters, step_lr, active, improved, r);
 }
-
-// The same with a running average of the output (--out_ema), with or without a held-out part: metrics = the raw iterate's doubles
-// (dpi_masked_loss[_holdout]), ema = those of the stored average (dpi_ema_loss).  History rows: the 4 (6 with a holdout) raw columns, then
-// {ema_loss, ema_snr[, ema_val_loss, ema_val_snr]}.  *improved, best_iter, early stopping and the NaN stop follow the average's selection
-// misfit q = ema_val_loss with a holdout, else ema_loss; ReduceLROnPlateau the raw training loss.
-// state (double[12]): {iter, loss_min (raw training), plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved,
-//                      val_min (raw held-out, holdout only), best_iter, q_min, reserved}
 __global__ void loop_control_ema_kernel(const double* __restrict__ metrics, const double* __restrict__ ema, int ho, double* __restrict__ state,
                                         double* __restrict__ hist, int max_iters, float* __restrict__ step_lr, int* __restrict__ active,
-                                        int* __restrict__ improved, int use_plateau, double factor, double threshold, int patience,
-                                        double min_lr, double lr_eps, int es_patience, double es_min_delta) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  *improved = 0;
-  if (!*active) return;
-  const int it = (int)state[0];
-  const double loss = metrics[0];
-  const double q = ho ? ema[8] : ema[0];
-  const double lr = (double)step_lr[1];
-  if (it < max_iters) {
-    double* row = hist + (ho ? 10 : 6) * (size_t)it;
-    row[0] = loss; row[1] = metrics[1]; row[2] = metrics[2]; row[3] = lr;
-    if (ho) { row[4] = metrics[8]; row[5] = metrics[9]; row += 2; }
-    row[4] = ema[0]; row[5] = ema[1];
-    if (ho) { row[6] = ema[8]; row[7] = ema[9]; }
-  }
-  if (it == 0 || loss <= state[1]) state[1] = loss;
-  if (ho && (it == 0 || metrics[8] <= state[8])) state[8] = metrics[8];
-  if (it == 0 || q <= state[10]) { state[10] = q; state[9] = (double)it; *improved = 1; }
-  if (use_plateau) {
-    if (loss < state[2] * (1.0 - threshold)) { state[2] = loss; state[3] = 0.0; }
-    else state[3] += 1.0;
-    if (state[3] > (double)patience) {
-      const double nl = fmax(lr * factor, min_lr);
-      if (lr - nl > lr_eps) step_lr[1] = (float)nl;
-      state[3] = 0.0;
-    }
-  }
-  if (es_patience != 0) {
-    if (state[6] == 0.0) { state[4] = q; state[6] = 1.0; }
-    else if (q != q) *active = 0;
-    else {
-      if (q < state[4] - state[4] * es_min_delta / 100.0) { state[5] = 0.0; state[4] = q; }
-      else state[5] += 1.0;
-      if (state[5] >= (double)es_patience) *active = 0;
-    }
-  }
-  state[0] = (double)(it + 1);
+                                        int* __restrict__ improved, dpi_loop_rules r) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) dpi_loop_rule(metrics, ema, ho != 0, state, hist, max_iters, step_lr, active, improved, r);
 }
 
 __global__ __launch_bounds__(256) void copy_if_kernel(const int* __restrict__ flag, const float* __restrict__ src, float* __restrict__ dst,
@@ -788,8 +682,8 @@ extern "C" int dpi_loop_control(const double* metrics, double* state, double* hi
                                 int* improved, int use_plateau, double factor, double threshold, int patience, double min_lr,
                                 double lr_eps, int es_patience, double es_min_delta, void* stream) {
   DPI_REQUIRE(metrics && state && hist && step_lr && active && improved && max_iters > 0, "loop_control: bad argument");
-  loop_control_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, use_plateau, factor,
-                                                        threshold, patience, min_lr, lr_eps, es_patience, es_min_delta);
+  loop_control_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, {use_plateau, factor,
+                                                        threshold, patience, min_lr, lr_eps, es_patience, es_min_delta});
   return dpi_check_launch("loop_control");
 }
 
@@ -797,8 +691,8 @@ extern "C" int dpi_loop_control_holdout(const double* metrics, double* state, do
                                         int* improved, int use_plateau, double factor, double threshold, int patience, double min_lr,
                                         double lr_eps, int es_patience, double es_min_delta, void* stream) {
   DPI_REQUIRE(metrics && state && hist && step_lr && active && improved && max_iters > 0, "loop_control_holdout: bad argument");
-  loop_control_holdout_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, use_plateau,
-                                                                factor, threshold, patience, min_lr, lr_eps, es_patience, es_min_delta);
+  loop_control_holdout_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, state, hist, max_iters, step_lr, active, improved, {use_plateau,
+                                                                factor, threshold, patience, min_lr, lr_eps, es_patience, es_min_delta});
   return dpi_check_launch("loop_control_holdout");
 }
 
@@ -808,8 +702,8 @@ extern "C" int dpi_loop_control_ema(const double* metrics, const double* ema_met
                                     void* stream) {
   DPI_REQUIRE(metrics && ema_metrics && state && hist && step_lr && active && improved && max_iters > 0, "loop_control_ema: bad argument");
   loop_control_ema_kernel<<<1, 64, 0, (hipStream_t)stream>>>(metrics, ema_metrics, has_holdout != 0, state, hist, max_iters, step_lr, active,
-                                                            improved, use_plateau, factor, threshold, patience, min_lr, lr_eps, es_patience,
-                                                            es_min_delta);
+                                                            improved, {use_plateau, factor, threshold, patience, min_lr, lr_eps, es_patience,
+                                                            es_min_delta});
   return dpi_check_launch("loop_control_ema");
 }
 

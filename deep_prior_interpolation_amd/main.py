@@ -15,6 +15,7 @@ from . import _lib, ops
 from . import utils as u
 from .architectures import build_net
 from .data import extract_patches
+from .loop import LoopRule
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
 from .parameter import check_avo, check_out_ema, check_trace_offsets_flag, net_args_are_same, parse_arguments
 
@@ -214,24 +215,14 @@ class Interpolator:
         opt = self.optimizer
         return ops.ema_loss(o, self._ema_avg, self.img_, self.mask_, self._holdout_dev, self.out_ema, opt.step_lr, opt.active, self.loss_kind)
 
-    def _select_ema(self, em):
-        """The eager loop's half of dpi_loop_control_ema, on the doubles of the same read-back: out_best follows the selection misfit of the
-        AVERAGE (ema_val_loss with --holdout, else ema_loss); the selected average is snapshot on the device (dpi_copy_if with a constant 1
-        flag: the next iteration overwrites the average itself)."""
-        ho = self._holdout_dev is not None
-        self.history.append_ema(em[0], em[1], *((em[8], em[9]) if ho else ()))
-        q = em[8] if ho else em[0]
-        improved, self.ema_min, self.best_iter = u.select_latest_min(self.iiter, q, self.ema_min, self.best_iter)
-        if improved:
-            _lib.check(_lib.load().dpi_copy_if(_lib.ptr(self._ema_one), _lib.ptr(self._ema_avg), _lib.ptr(self._ema_best),
-                                               self._ema_avg.numel(), _lib.stream()), "dpi_copy_if")
-            self._out_best_dev = self._ema_best
-        self._last_val = q
+    def loop_rule(self):
+        """The loop-control layout of the loaded patch (loop.LoopRule): with or without a held-out part and a running average."""
+        return LoopRule(self._holdout_dev is not None, self.out_ema > 0.0)
 
     def _read_back(self, metrics, ema):
         """The one read-back of an iteration: the raw iterate's doubles and, with --out_ema, the average's."""
         if ema is None:
-            return (metrics[:10] if self._holdout_dev is not None else metrics[:3]).tolist(), None
+            return metrics[:self.loop_rule().metrics_doubles].tolist(), None
         both = torch.cat([metrics, ema]).tolist()
         return both[:metrics.numel()], both[metrics.numel():]
 
@@ -517,45 +508,38 @@ class Interpolator:
             self.input_list.append(u.torch_to_np(input_, True))
         out_, ema, total_loss, metrics = self._forward_and_loss(input_)
         reg = self.regularization(out_, total_loss)          # None, or (weight tensor / float, reg loss) of a subclass / add-on
+        total = total_loss if reg is None else total_loss + reg[0] * reg[1]
+        total.backward()
+        ops.finish_backward(self._grad_params())
+        m, em = self._read_back(metrics, ema)                  # one read-back
+        l, s, p = m[:3]
         if reg is None:
-            total_loss.backward()
-            ops.finish_backward(self._grad_params())
-            m, em = self._read_back(metrics, ema)                  # one read-back
-            l, s, p = m[:3]
             self.history.append((l, s, p))
         else:
-            eps, reg_loss = reg
-            total = total_loss + eps * reg_loss
-            total.backward()
-            ops.finish_backward(self._grad_params())
-            m, em = self._read_back(metrics, ema)
-            main_l, s, p = m[:3]
-            l, r = float(total.item()), float(reg_loss.item())
-            self.history.append((l, main_l, r, s, p))           # HistoryReg layout (main_pocs.py:198-202)
+            main_l, l = l, float(total.item())                 # the loop follows the total
+            self.history.append((l, main_l, float(reg[1].item()), s, p))          # HistoryReg layout (main_pocs.py:198-202)
         self.history.lr.append(self.optimizer.param_groups[0]["lr"])
-        if em is not None:
-            # --out_ema: the raw columns as ever, the selection from the average
-            if self.iiter == 0 or l <= self.loss_min:
-                self.loss_min = l
-            if self._holdout_dev is not None:
-                self.history.append_val(m[8], m[9])
-                if self.iiter == 0 or m[8] <= self.val_min:
-                    self.val_min = m[8]
-            self._select_ema(em)
-        elif self._holdout_dev is None:
-            if self.iiter == 0 or l <= self.loss_min:
-                self.loss_min = l
-                self._out_best_dev = out_.detach()   # stays on the GPU; copied to the host once, after the loop
-        else:
-            # --holdout: out_best follows the misfit on the held-out traces (the later iterate wins a tie, as main.py:173-180 does on loss)
-            val, vsnr = m[8], m[9]
-            self.history.append_val(val, vsnr)
-            if self.iiter == 0 or l <= self.loss_min:
-                self.loss_min = l
-            if self.iiter == 0 or val <= self.val_min:
-                self.val_min, self.best_iter = val, self.iiter
-                self._out_best_dev = out_.detach()
-            self._last_val = val
+        # the rule of csrc/loop_rule.h on the doubles of the same read-back: the raw columns and minima as ever, the selection on q —
+        # decided before a minimum is written, as q's minimum may be loss_min / val_min itself
+        rule, it = self.loop_rule(), self.iiter
+        if rule.holdout:
+            self.history.append_val(m[8], m[9])
+        if rule.ema:
+            self.history.append_ema(em[0], em[1], *((em[8], em[9]) if rule.holdout else ()))
+        improved, q_min, best_iter = u.select_latest_min(it, rule.q(self.history), getattr(self, rule.q_min_attr), self.best_iter)
+        self.loss_min = u.select_latest_min(it, l, self.loss_min, None)[1]
+        if rule.holdout:
+            self.val_min = u.select_latest_min(it, m[8], self.val_min, None)[1]
+        setattr(self, rule.q_min_attr, q_min)
+        if rule.tracks_best_iter:
+            self.best_iter = best_iter
+        if improved and rule.ema:
+            # the selected average is snapshot on the device (dpi_copy_if with a constant 1 flag: the next iteration overwrites the average)
+            _lib.check(_lib.load().dpi_copy_if(_lib.ptr(self._ema_one), _lib.ptr(self._ema_avg), _lib.ptr(self._ema_best),
+                                               self._ema_avg.numel(), _lib.stream()), "dpi_copy_if")
+            self._out_best_dev = self._ema_best
+        elif improved:
+            self._out_best_dev = out_.detach()       # stays on the GPU; copied to the host once, after the loop
         if self.iiter in self.iter_to_be_saved and self.iiter != 0:
             np.save(os.path.join(self.outpath, self.image_name.split(".")[0]
                                  + "_output%s.npy" % str(self.iiter).zfill(self.zfill)), self._to_numpy_out(out_))
@@ -648,15 +632,13 @@ class Interpolator:
         self._ensure_holdout()
         big = self.wants_weight_grad_overlap()
         if mode == "auto":
-            # big fp32 patches are GPU-bound either way and gain from overlapping the weight gradients (eager only);
-            # small ones are launch-bound without a graph
-            # big patches run eager with the weight-gradient / branch streams (`big`).  With those switched off (DPI_FORCE_OVERLAP=0) a
-            # big patch is captured only for long runs: the capture allocates a memory pool of its own — as much again as one
-            # iteration's activations, 20 GB at 512x256x256 — and costs 0.1-3 s of hipMalloc / instantiation depending on the box (measured
-            # on configs[4], 30 iterations per patch: 160-210 ms per iteration with the capture, 113 ms eager)
-            large = int(np.prod(self.img.shape[:-1])) >= (1 << 20)
-            mode = "eager" if (net_inputs is not None or a.save_every is not None or a.epochs < 3 or self.has_regularizer()
-                               or a.data_forgetting_factor != 0 or self.noise_source() != "philox" or big or (large and a.epochs < 1000)) else "graph"
+            # small patches are launch-bound without a graph; big ones run eager with the weight-gradient / branch streams (`big`)
+            reasons = self._eager_reasons(net_inputs)
+            # the one difference from graph_capable(): a big patch WITHOUT those streams (DPI_FORCE_OVERLAP=0, --net part) is captured when the
+            # run is long: the capture allocates a memory pool of its own — as much again as one iteration's activations, 20 GB at
+            # 512x256x256 — and costs 0.1-3 s of hipMalloc / instantiation depending on the box (measured on configs[4], 30 iterations per
+            # patch: 160-210 ms per iteration with the capture, 113 ms eager)
+            mode = "graph" if (not reasons or (reasons == ["size"] and not big and a.epochs >= 1000)) else "eager"
         self.optimizer = self.make_optimizer()
         ops.set_weight_grad_overlap(big, in_graph=(mode == "graph" and big))
         start = time()
@@ -675,7 +657,7 @@ class Interpolator:
                     sched.step(loss)
                 if verbose:
                     print(self.history.log_message(self.iiter - 1), "\r", end="")
-                if stopper.step(loss if (self._holdout_dev is None and self.out_ema == 0.0) else self._last_val):
+                if stopper.step(self.loop_rule().q(self.history)):          # the selection misfit the loop itself followed
                     break
             torch.cuda.synchronize(self.device)
             self.out_best = self._to_numpy_out(self._out_best_dev)
@@ -719,15 +701,8 @@ class Interpolator:
             ops.set_weight_grad_overlap(big, in_graph=big)
         opt = self.optimizer
         self._ensure_holdout()
-        ho = self._holdout_dev
-        ema_on = self.out_ema > 0.0
-        # history row {loss, snr, pcorr, lr[, val_loss, val_snr][, ema_loss, ema_snr[, ema_val_loss, ema_val_snr]]}
-        cols = (4 if ho is None else 6) + ((2 if ho is None else 4) if ema_on else 0)
-        self._g_layout = (ho is not None, ema_on)
-        self._g_state = torch.zeros(12 if ema_on else (8 if ho is None else 10), dtype=torch.float64, device=dev)
-        self._g_state[2] = float("inf")
-        self._g_hist = torch.zeros(a.epochs * cols, dtype=torch.float64, device=dev)
-        self._g_improved = torch.zeros(1, dtype=torch.int32, device=dev)
+        rule = self._g_rule = self.loop_rule()
+        self._g_state, self._g_hist, self._g_improved = rule.new_state(a.epochs, dev)
         self._g_best = None
 
         def one_iteration():
@@ -744,16 +719,9 @@ class Interpolator:
             if self._g_best is None:
                 self._g_best = torch.empty_like(out_)
             rules = (int(bool(a.reduce_lr)), float(a.lr_factor), float(a.lr_thresh), int(a.lr_patience), 0.0, 1e-8,
-                     int(a.earlystop_patience), float(a.earlystop_min_delta), _lib.stream())
-            if ema_on:
-                _lib.check(L.dpi_loop_control_ema(_lib.ptr(metrics), _lib.ptr(ema), int(ho is not None), _lib.ptr(self._g_state),
-                                                  _lib.ptr(self._g_hist), a.epochs, _lib.ptr(opt.step_lr), _lib.ptr(opt.active),
-                                                  _lib.ptr(self._g_improved), *rules), "dpi_loop_control_ema")
-            else:
-                control = L.dpi_loop_control if ho is None else L.dpi_loop_control_holdout
-                _lib.check(control(_lib.ptr(metrics), _lib.ptr(self._g_state), _lib.ptr(self._g_hist), a.epochs,
-                                   _lib.ptr(opt.step_lr), _lib.ptr(opt.active), _lib.ptr(self._g_improved), *rules), "dpi_loop_control")
-            best_src = self._ema_avg if ema_on else out_         # --out_ema: the selected AVERAGE is kept
+                     int(a.earlystop_patience), float(a.earlystop_min_delta))
+            rule.launch(metrics, ema, self._g_state, self._g_hist, a.epochs, opt.step_lr, opt.active, self._g_improved, rules)
+            best_src = self._ema_avg if rule.ema else out_       # --out_ema: the selected AVERAGE is kept
             _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(best_src), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
 
@@ -783,23 +751,9 @@ class Interpolator:
             torch.cuda.synchronize(self.device)
         else:
             torch.cuda.current_stream(self.device).synchronize()
-        n = int(self._g_state[0].item())
-        cols = self._g_hist.numel() // self.args.epochs
-        h = self._g_hist[:cols * n].view(n, cols).cpu().numpy()
+        n, h, st = self._g_rule.rows(self._g_state, self._g_hist)
         self.history = self._new_history()
-        self.history.loss, self.history.snr, self.history.pcorr, self.history.lr = (h[:, i].tolist() for i in range(4))
-        self.loss_min = float(self._g_state[1].item())
-        ho, ema_on = self._g_layout
-        k = 4
-        if ho:
-            self.history.val_loss, self.history.val_snr = h[:, 4].tolist(), h[:, 5].tolist()
-            self.val_min, self.best_iter = float(self._g_state[8].item()), int(self._g_state[9].item())
-            k = 6
-        if ema_on:
-            self.history.ema_loss, self.history.ema_snr = h[:, k].tolist(), h[:, k + 1].tolist()
-            if ho:
-                self.history.ema_val_loss, self.history.ema_val_snr = h[:, k + 2].tolist(), h[:, k + 3].tolist()
-            self.best_iter, self.ema_min = int(self._g_state[9].item()), float(self._g_state[10].item())
+        self._g_rule.fill(self, self.history, h, st)
         self.iiter = n
         self._out_best_dev = self._g_best
         self.out_best = self._to_numpy_out(self._g_best)
@@ -813,27 +767,27 @@ class Interpolator:
                 if int(self.optimizer.active.item()) == 0:     # early stop / NaN decided on the device
                     break
                 if verbose:
-                    n = int(self._g_state[0].item())
-                    cols = self._g_hist.numel() // self.args.epochs
-                    row = self._g_hist[cols * (n - 1):cols * n].tolist()
-                    msg = "Iter %d, Loss = %+.2e, SNR = %+2.2f dB, PCORR = %+.2f %%" % (n, row[0], row[1], row[2] * 100)
-                    ho, ema_on = self._g_layout
-                    if ho:
-                        msg += ", VAL = %.2e, VSNR = %+.2f dB" % (row[4], row[5])
-                    if ema_on:
-                        msg += ", ESNR = %+.2f dB" % row[7 if ho else 5]
-                    print(msg, "\r", end="")
+                    n, h, _ = self._g_rule.rows(self._g_state, self._g_hist)
+                    print(self._g_rule.progress(n, h[-1]), "\r", end="")
         self.graph_finish()
 
     def has_regularizer(self):
         return getattr(self, "_aa_op", None) is not None
 
-    def graph_capable(self):
-        """True when optimize(mode='auto') would take the hipGraph path for the loaded patch."""
+    def _eager_reasons(self, net_inputs=None):
+        """Why the loaded patch is optimised eagerly instead of from a captured iteration: each reason once, for optimize(mode='auto')
+        and graph_capable()."""
         a = self.args
-        return not (a.save_every is not None or a.epochs < 3 or a.data_forgetting_factor != 0 or self.has_regularizer()
-                    or self.noise_source() != "philox"
-                    or int(np.prod(self.img.shape[:-1])) >= (1 << 20))
+        return [name for name, holds in (
+            ("per-iteration host work", net_inputs is not None or a.save_every is not None or a.epochs < 3),
+            ("regulariser", self.has_regularizer()),
+            ("data forgetting", a.data_forgetting_factor != 0),
+            ("noise source", self.noise_source() != "philox"),
+            ("size", int(np.prod(self.img.shape[:-1])) >= (1 << 20))) if holds]       # >= 2^20 voxels: GPU-bound either way
+
+    def graph_capable(self):
+        """True when the loaded patch can share the GPU as one of several captured iterations (parallel.py asks)."""
+        return not self._eager_reasons()
 
     # ------------------------------------------------------------------------------------------
     def save_result(self):

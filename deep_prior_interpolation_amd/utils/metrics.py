@@ -218,7 +218,7 @@ def history_class(reg=False, holdout=False, ema=False):
 def select_latest_min(it, misfit, best, best_iter):
     """The selection rule of the loop, one iteration of it: (improved, best, best_iter) after iteration `it` (0-based) showed `misfit`.
     Iteration 0 always selects; later ones when misfit <= best, so the later iterate wins a tie and a NaN never selects (after a NaN at
-    iteration 0 nothing does).  The device rule of dpi_loop_control_ema, on the same doubles."""
+    iteration 0 nothing does).  The selection of the one device rule (dpi_loop_rule, csrc/loop_rule.h), on the same doubles."""
     if it == 0 or misfit <= best:
         return True, misfit, it
     return False, best, best_iter

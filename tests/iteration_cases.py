@@ -412,25 +412,61 @@ def loop_cfg(**kw):
     return dict(LoopCfg, **kw)
 
 
-def new_loop_state():
-    st = np.zeros(8)
+LOOP_VARIANTS = {"plain": (0, 0), "holdout": (1, 0), "ema": (0, 1), "ema-holdout": (1, 1)}      # name: (held-out part, running average)
+
+
+def loop_layout(variant):
+    """(state doubles, history columns): state {iter, loss_min, plateau_best, plateau_bad, es_best, es_bad, es_has_best, reserved} of the
+    plain entry point, + {val_min, best_iter} with a held-out part, + {q_min, reserved} with a running average (which has slots 8 and 9
+    with or without a held-out part); rows {loss, snr, pcorr, lr[, val_loss, val_snr][, ema_loss, ema_snr[, ema_val_loss, ema_val_snr]]}."""
+    ho, ema = LOOP_VARIANTS[variant]
+    return (12 if ema else 10 if ho else 8), 4 + 2 * ho + ema * (2 + 2 * ho)
+
+
+def new_loop_state(variant="plain"):
+    st = np.zeros(loop_layout(variant)[0])
     st[2] = np.inf
     return st
 
 
-def loop_control_step(metrics, state, hist, max_iters, step_lr, active, cfg, mutation=None):
-    """One call of loop_control_kernel on host copies: metrics [>= 3] doubles, state [8] doubles, hist [4 max_iters] doubles, step_lr [2]
-    fp32, active int.  Everything is updated in place; returns (improved, active).  mutation "improved<": `<` in place of `<=`."""
+def loop_control_step(metrics, state, hist, max_iters, step_lr, active, cfg, mutation=None, variant="plain", ema=None):
+    """One call of dpi_loop_control (plain), dpi_loop_control_holdout or dpi_loop_control_ema on host copies: metrics [>= 3] doubles ([>= 10]
+    with a held-out part), ema the average's doubles, state and hist as loop_layout says, step_lr [2] fp32, active int.  Everything is
+    updated in place; returns (improved, active).  The selection misfit q — loss; val_loss = metrics[8] with a held-out part; the
+    average's ema[0], or ema[8] with a held-out part — drives *improved, best_iter, early stopping and the NaN stop; its minimum lives in
+    state[1], state[8] (which is the raw val_min as well) or state[10].  ReduceLROnPlateau follows the raw training loss.
+    mutation "improved<": `<` in place of `<=` in the selection."""
     if not active:
         return 0, 0
+    ho, has_ema = LOOP_VARIANTS[variant]
     improved = 0
     it = int(state[0])
     loss = float(metrics[0])
     lr = float(step_lr[1])
+    row = [loss, metrics[1], metrics[2], lr] + ([metrics[8], metrics[9]] if ho else [])
+    if has_ema:
+        row += [ema[0], ema[1]] + ([ema[8], ema[9]] if ho else [])
     if it < max_iters:
-        hist[4 * it:4 * it + 4] = [loss, metrics[1], metrics[2], lr]
-    if it == 0 or (loss < state[1] if mutation == "improved<" else loss <= state[1]):
-        state[1], improved = loss, 1
+        hist[len(row) * it:len(row) * (it + 1)] = row
+    better = lambda x, best: it == 0 or (x < best if mutation == "improved<" else x <= best)
+    if has_ema:                                                  # raw minima, then the selection on the average's misfit
+        if it == 0 or loss <= state[1]:
+            state[1] = loss
+        if ho and (it == 0 or metrics[8] <= state[8]):
+            state[8] = metrics[8]
+        q = float(ema[8] if ho else ema[0])
+        if better(q, state[10]):
+            state[10], state[9], improved = q, float(it), 1
+    elif ho:
+        if it == 0 or loss <= state[1]:
+            state[1] = loss
+        q = float(metrics[8])
+        if better(q, state[8]):
+            state[8], state[9], improved = q, float(it), 1
+    else:
+        q = loss
+        if better(q, state[1]):
+            state[1], improved = loss, 1
     if cfg["use_plateau"]:
         if loss < state[2] * (1.0 - cfg["threshold"]):
             state[2], state[3] = loss, 0.0
@@ -443,12 +479,12 @@ def loop_control_step(metrics, state, hist, max_iters, step_lr, active, cfg, mut
             state[3] = 0.0
     if cfg["es_patience"] != 0:
         if state[6] == 0.0:
-            state[4], state[6] = loss, 1.0
-        elif loss != loss:
+            state[4], state[6] = q, 1.0
+        elif q != q:
             active = 0
         else:
-            if loss < state[4] - state[4] * cfg["es_min_delta"] / 100.0:
-                state[5], state[4] = 0.0, loss
+            if q < state[4] - state[4] * cfg["es_min_delta"] / 100.0:
+                state[5], state[4] = 0.0, q
             else:
                 state[5] += 1.0
             if state[5] >= float(cfg["es_patience"]):
@@ -457,13 +493,31 @@ def loop_control_step(metrics, state, hist, max_iters, step_lr, active, cfg, mut
     return improved, active
 
 
-def loop_control_run(losses, lr0, max_iters, cfg, mutation=None):
-    """The model over a loss sequence (snr = 10 + it, pcorr = 0.5).  Returns a list of per-call records (improved, active, lr after the
-    call, a copy of the state) and the history; stops calling once *active is 0, as a driver does."""
-    state, hist = new_loop_state(), np.full(4 * max_iters, np.nan)
+def loop_inputs(variant, it, loss, q=None):
+    """(metrics, ema doubles or None) of call `it`: snr = 10 + it, pcorr = 0.5; with a held-out part val_snr = 20 + it and val_loss = q,
+    or 3 + it under a running average, whose own doubles carry q where the selection reads it and a decoy that would select differently
+    in the other misfit slot."""
+    ho, has_ema = LOOP_VARIANTS[variant]
+    if not ho and not has_ema:
+        return loop_metrics(it, loss), None
+    m = np.zeros(11)
+    m[[0, 1, 2, 8, 9]] = [loss, 10.0 + it, 0.5, 3.0 + it if has_ema else q, 20.0 + it]
+    if not has_ema:
+        return m, None
+    e = np.zeros(11)
+    e[[0, 1, 8, 9]] = [5.0 + it, 30.0 + it, q, 40.0 + it] if ho else [q, 30.0 + it, 5.0 - it, 40.0 + it]
+    return m, e
+
+
+def loop_control_run(losses, lr0, max_iters, cfg, mutation=None, variant="plain", qs=None):
+    """The model over a loss sequence (and, for the other variants, the sequence qs of selection misfits), inputs as loop_inputs builds
+    them.  Returns a list of per-call records (improved, active, lr after the call, a copy of the state) and the history; stops calling
+    once *active is 0, as a driver does."""
+    state, hist = new_loop_state(variant), np.full(loop_layout(variant)[1] * max_iters, np.nan)
     step_lr, active, log = np.array([1.0, lr0], dtype=F), 1, []
     for it, loss in enumerate(losses):
-        improved, active = loop_control_step(loop_metrics(it, loss), state, hist, max_iters, step_lr, active, cfg, mutation)
+        metrics, ema = loop_inputs(variant, it, loss, None if qs is None else qs[it])
+        improved, active = loop_control_step(metrics, state, hist, max_iters, step_lr, active, cfg, mutation, variant, ema)
         log.append((improved, active, float(step_lr[1]), state.copy()))
         if not active:
             break
@@ -471,11 +525,12 @@ def loop_control_run(losses, lr0, max_iters, cfg, mutation=None):
 
 
 def check_loop_log(got, want, what):
-    """Per call: *improved, *active, the bits of step_lr[1] and the eight state doubles (a NaN equals a NaN)."""
+    """Per call: *improved, *active, the bits of step_lr[1] and every state double (a NaN equals a NaN)."""
     assert len(got) == len(want), (what, len(got), len(want))
     for it, (g, w) in enumerate(zip(got, want)):
         assert (g[0], g[1]) == (w[0], w[1]), "%s: call %d: (improved, active) = %s, model %s" % (what, it, g[:2], w[:2])
         assert bits(F(g[2])) == bits(F(w[2])), "%s: call %d: lr %r, model %r" % (what, it, g[2], w[2])
+        assert np.asarray(g[3]).shape == np.asarray(w[3]).shape, (what, it)
         np.testing.assert_array_equal(np.asarray(g[3]), np.asarray(w[3]), err_msg="%s: state after call %d" % (what, it))
 
 
@@ -496,6 +551,69 @@ LOOP_SCRIPTS = {                                  # name: (losses, cfg, max_iter
     "no-plateau": ([1.0] * 8, loop_cfg(use_plateau=0, factor=0.5, threshold=0.1, patience=1), None),
     "past-max-iters": ([1.0, 0.9, 0.8, 0.8, 0.8, 0.7], loop_cfg(use_plateau=1, factor=0.5, threshold=0.1, patience=1), 3),
 }
+
+# Scripts of the other variants, shared by the host and the device tests.  name: (rows, ReduceLROnPlateau (factor, threshold, patience) or
+# None, EarlyStopping (patience, min_delta %)).  --holdout: rows of (training loss, val_loss)
+HOLDOUT_SCRIPTS = {
+    "ties": ([(1.0, 1.0), (0.9, 1.0), (0.8, 0.7), (0.85, 0.7), (0.7, 0.75), (0.6, 0.7)], None, (0, 1.0)),
+    "rising": ([(1.0, 1.0), (0.9, 0.95), (0.8, 1.1), (0.7, 1.2), (0.6, 1.3), (0.5, 1.4), (0.4, 0.1)], None, (3, 1.0)),
+    "nan": ([(1.0, 1.0), (0.9, 0.8), (0.8, NAN), (0.7, 0.5), (0.6, 0.4)], None, (5, 1.0)),
+    "plateau": ([(1.0, 1.0 - 0.05 * k) for k in range(12)], (0.5, 0.1, 1), (4, 1.0)),        # flat training loss, falling val_loss
+}
+# --out_ema: rows of (raw training loss, the average's selection misfit)
+EMA_SCRIPTS = {
+    "ties": ([(1.0, 1.0), (0.9, 1.0), (0.8, 0.7), (0.85, 0.7), (0.7, 0.75), (0.6, 0.7)], None, (0, 1.0)),
+    "rising": ([(1.0, 1.0), (0.9, 0.95), (0.8, 1.1), (0.7, 1.2), (0.6, 1.3), (0.5, 1.4), (0.4, 0.1)], None, (3, 1.0)),      # stops on q while the raw loss falls
+    "nan": ([(1.0, 1.0), (0.9, 0.8), (0.8, NAN), (0.7, 0.5), (0.6, 0.4)], None, (5, 1.0)),
+    "nan_raw": ([(1.0, 1.0), (NAN, 0.8), (0.8, 0.7), (0.7, 0.9)], None, (5, 1.0)),                                        # a NaN raw loss does not stop the loop
+    "plateau": ([(1.0, 1.0 - 0.05 * k) for k in range(12)], (0.5, 0.1, 1), (4, 1.0)),        # flat raw loss: lr cuts; falling q: no stop
+}
+
+
+def script_cfg(plateau, es):
+    """The loop_cfg of a row of HOLDOUT_SCRIPTS / EMA_SCRIPTS, with the constants their device tests pass (min_lr 0, lr_eps 1e-8)."""
+    factor, threshold, patience = plateau if plateau else (0.9, 1e-5, 100)
+    return loop_cfg(use_plateau=int(plateau is not None), factor=factor, threshold=threshold, patience=patience, es_patience=es[0],
+                    es_min_delta=es[1])
+
+
+def eager_loop_model(rows, lr0, plateau, es):
+    """The eager loop's rules over rows of (training loss, selection misfit q): best on q (utils.select_latest_min: <=, the later iterate
+    wins), utils.EarlyStopping on q, the ReduceLROnPlateau arithmetic on the training loss.  Per call (improved, lr used, best_iter)."""
+    from deep_prior_interpolation_amd import utils as u
+    stopper = u.EarlyStopping(patience=es[0], min_delta=es[1], percentage=True)
+    best, bad, lr = float("inf"), 0, np.float32(lr0)
+    qmin, best_iter, log = None, None, []
+    for it, (loss, q) in enumerate(rows):
+        improved, qmin, best_iter = u.select_latest_min(it, q, qmin, best_iter)
+        lr_used = lr
+        if plateau is not None:
+            factor, thr, pat = plateau
+            if loss < best * (1.0 - thr):
+                best, bad = loss, 0
+            else:
+                bad += 1
+            if bad > pat:
+                nl = max(float(lr) * factor, 0.0)
+                if float(lr) - nl > 1e-8:
+                    lr = np.float32(nl)
+                bad = 0
+        stop = stopper.step(q)
+        log.append((int(improved), float(lr_used), best_iter))
+        if stop:
+            break
+    return log
+
+
+def variant_scripts(variant):
+    """name: (losses, qs or None, cfg, max_iters) — LOOP_SCRIPTS for the plain variant, for the others the table they belong to and the
+    past-the-end case (six calls on a history of three rows; q falls, rises and ties while the flat loss cuts the lr)."""
+    if variant == "plain":
+        return {k: (losses, None, cfg, n or len(losses)) for k, (losses, cfg, n) in LOOP_SCRIPTS.items()}
+    table = HOLDOUT_SCRIPTS if variant == "holdout" else EMA_SCRIPTS
+    out = {k: ([r[0] for r in rows], [r[1] for r in rows], script_cfg(plateau, es), len(rows)) for k, (rows, plateau, es) in table.items()}
+    out["past-max-iters"] = ([1.0] * 6, [1.0, 0.9, 0.95, 0.9, 0.8, 0.85], LOOP_SCRIPTS["past-max-iters"][1], 3)
+    return out
 
 
 # ---- overlap-add -------------------------------------------------------------------------------------------------------------------------

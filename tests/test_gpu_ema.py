@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import iteration_cases as I
 from conftest import jstr
 from gpu_guard import guard
 
@@ -167,41 +168,7 @@ def test_inactive_leaves_average_and_result_alone(with_sel):
 
 
 # ---------------------------------------------------------------- loop control ----------------------------------------------------------
-def _host_model(rows, lr0, plateau, es):
-    """The eager loop's rules: best on the average's misfit q (select_latest_min), EarlyStopping on q, ReduceLROnPlateau on the raw loss."""
-    from deep_prior_interpolation_amd import utils as u
-    stopper = u.EarlyStopping(patience=es[0], min_delta=es[1], percentage=True)
-    best, bad, lr = float("inf"), 0, np.float32(lr0)
-    qmin, best_iter, log = None, None, []
-    for it, (loss, q) in enumerate(rows):
-        improved, qmin, best_iter = u.select_latest_min(it, q, qmin, best_iter)
-        lr_used = lr
-        if plateau is not None:
-            factor, thr, pat = plateau
-            if loss < best * (1.0 - thr):
-                best, bad = loss, 0
-            else:
-                bad += 1
-            if bad > pat:
-                nl = max(float(lr) * factor, 0.0)
-                if float(lr) - nl > 1e-8:
-                    lr = np.float32(nl)
-                bad = 0
-        stop = stopper.step(q)
-        log.append((int(improved), float(lr_used), best_iter))
-        if stop:
-            break
-    return log
-
-
-# rows of (raw training loss, the average's selection misfit)
-SCRIPTS = {
-    "ties": ([(1.0, 1.0), (0.9, 1.0), (0.8, 0.7), (0.85, 0.7), (0.7, 0.75), (0.6, 0.7)], None, (0, 1.0)),
-    "rising": ([(1.0, 1.0), (0.9, 0.95), (0.8, 1.1), (0.7, 1.2), (0.6, 1.3), (0.5, 1.4), (0.4, 0.1)], None, (3, 1.0)),      # stops on q while the raw loss falls
-    "nan": ([(1.0, 1.0), (0.9, 0.8), (0.8, float("nan")), (0.7, 0.5), (0.6, 0.4)], None, (5, 1.0)),
-    "nan_raw": ([(1.0, 1.0), (float("nan"), 0.8), (0.8, 0.7), (0.7, 0.9)], None, (5, 1.0)),                               # a NaN raw loss does not stop the loop
-    "plateau": ([(1.0, 1.0 - 0.05 * k) for k in range(12)], (0.5, 0.1, 1), (4, 1.0)),        # flat raw loss: lr cuts; falling q: no stop
-}
+SCRIPTS = I.EMA_SCRIPTS          # shared with the host tests (tests/iteration_cases.py), as is the model of the eager rules
 
 
 @pytest.mark.parametrize("ho", [0, 1])
@@ -211,7 +178,7 @@ def test_loop_control_against_host_model(name, ho):
     L = _lib.load()
     rows, plateau, es = SCRIPTS[name]
     lr0, cols = 1e-3, 10 if ho else 6
-    ref = _host_model(rows, lr0, plateau, es)
+    ref = I.eager_loop_model(rows, lr0, plateau, es)
     metrics = torch.zeros(11, dtype=torch.float64, device=DEV)
     ema = torch.zeros(11, dtype=torch.float64, device=DEV)
     state = torch.zeros(12, dtype=torch.float64, device=DEV)

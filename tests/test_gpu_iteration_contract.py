@@ -435,21 +435,32 @@ def test_noise_non_temporal_path(lib):
 
 
 # ---- 4. loop control and dpi_copy_if -----------------------------------------------------------------------------------------------------
-def loop_run_device(lib, losses, lr0, max_iters, cfg, extra_gated_calls=0):
-    """dpi_loop_control over a loss sequence on guarded buffers of exactly the documented sizes; the log and history in the form of
-    iteration_cases.loop_control_run.  After the sequence (or the stop) `extra_gated_calls` more calls are made with *active == 0."""
+def loop_run_device(lib, losses, lr0, max_iters, cfg, extra_gated_calls=0, variant="plain", qs=None):
+    """dpi_loop_control (or the entry point of `variant`) over a loss sequence on guarded buffers of exactly the documented sizes —
+    metrics and ema of 8 doubles, 11 with a held-out part; state and hist as iteration_cases.loop_layout says; the log and history in the
+    form of iteration_cases.loop_control_run.  After the sequence (or the stop) `extra_gated_calls` more calls are made with *active == 0."""
     L = lib.load()
-    metrics, state = gin(I.loop_metrics(0, 0.0), F64), gin(I.new_loop_state(), F64)
-    hist = gout(4 * max_iters, F64)
+    ho, has_ema = I.LOOP_VARIANTS[variant]
+    n_state, cols = I.loop_layout(variant)
+    inputs = lambda it, loss: [None if x is None else x[:11 if ho else 8] for x in I.loop_inputs(variant, it, loss, None if qs is None else qs[min(it, len(qs) - 1)])]
+    metrics, ema = (None if x is None else gin(x, F64) for x in inputs(0, 0.0))
+    state = gin(I.new_loop_state(variant), F64)
+    assert state.payload.numel() == n_state
+    hist = gout(cols * max_iters, F64)
     step_lr = gin(np.array([1.0, lr0], dtype=F))
     active, improved = gints([1], torch.int32), gints([7], torch.int32)
     guards = [("metrics", metrics), ("state", state), ("hist", hist), ("step_lr", step_lr), ("active", active), ("improved", improved)]
+    guards += [("ema", ema)] if has_ema else []
     args = (cfg["use_plateau"], cfg["factor"], cfg["threshold"], cfg["patience"], cfg["min_lr"], cfg["lr_eps"], cfg["es_patience"], cfg["es_min_delta"])
+    entry = L.dpi_loop_control_ema if has_ema else (L.dpi_loop_control_holdout if ho else L.dpi_loop_control)
+    head = (ptr(metrics), ptr(ema), ho) if has_ema else (ptr(metrics),)
 
     def call(it, loss):
-        metrics.payload.copy_(torch.from_numpy(I.loop_metrics(it, loss)))
+        for g, x in zip((metrics, ema), inputs(it, loss)):
+            if g is not None:
+                g.payload.copy_(torch.from_numpy(x))
         improved.payload.view(torch.int32).fill_(7)
-        _launch(lib, L.dpi_loop_control(ptr(metrics), ptr(state), ptr(hist), max_iters, ptr(step_lr), ptr(active), ptr(improved), *args, lib.stream()),
+        _launch(lib, entry(*head, ptr(state), ptr(hist), max_iters, ptr(step_lr), ptr(active), ptr(improved), *args, lib.stream()),
                 "loop_control call %d" % it)
         _check_guards(guards, "loop_control call %d" % it)
     log = []
@@ -468,16 +479,18 @@ def loop_run_device(lib, losses, lr0, max_iters, cfg, extra_gated_calls=0):
     return log, host(hist)
 
 
-@pytest.mark.parametrize("name", sorted(I.LOOP_SCRIPTS))
-def test_loop_control_scripts(lib, name):
-    """The plain dpi_loop_control against the host model, call by call: *improved, *active, step_lr[1] and the eight state doubles
-    bit-equal, the history rows equal and NaN where no row was written.  `past-max-iters` has hist of 4 x 3 doubles and six calls: the
-    later ones leave hist alone and still advance state[0]."""
-    losses, cfg, max_iters = I.LOOP_SCRIPTS[name]
-    max_iters = max_iters or len(losses)
-    want, want_hist = I.loop_control_run(losses, 1e-3, max_iters, cfg)
-    got, got_hist = loop_run_device(lib, losses, 1e-3, max_iters, cfg, extra_gated_calls=2)
-    I.check_loop_log(got, want, "loop_control " + name)
+LOOP_CASES = [pytest.param(v, k, id=k if v == "plain" else v + "-" + k) for v in I.LOOP_VARIANTS for k in sorted(I.variant_scripts(v))]
+
+
+@pytest.mark.parametrize("variant, name", LOOP_CASES)
+def test_loop_control_scripts(lib, variant, name):
+    """dpi_loop_control, dpi_loop_control_holdout and dpi_loop_control_ema (with and without a held-out part) against the host model,
+    call by call: *improved, *active, step_lr[1] and every state double (8 / 10 / 12) bit-equal, the history rows equal and NaN where no
+    row was written.  `past-max-iters` has hist of three rows and six calls: the later ones leave hist alone and still advance state[0]."""
+    losses, qs, cfg, max_iters = I.variant_scripts(variant)[name]
+    want, want_hist = I.loop_control_run(losses, 1e-3, max_iters, cfg, variant=variant, qs=qs)
+    got, got_hist = loop_run_device(lib, losses, 1e-3, max_iters, cfg, extra_gated_calls=2, variant=variant, qs=qs)
+    I.check_loop_log(got, want, "loop_control %s %s" % (variant, name))
     np.testing.assert_array_equal(got_hist, want_hist)
     if name == "past-max-iters":
         assert got[-1][3][0] == len(losses) > max_iters and np.isfinite(got_hist).all()

@@ -344,6 +344,96 @@ def test_loop_control_with_a_strict_comparison_fails_the_check():
     assert _fails(lambda: I.check_loop_log(got, want, "strict"))
 
 
+def test_loop_control_holdout_with_a_strict_comparison_fails_the_check():
+    seq, qs, cfg, n = I.variant_scripts("holdout")["ties"]
+    want, _ = I.loop_control_run(seq, 1e-3, n, cfg, variant="holdout", qs=qs)
+    got, _ = I.loop_control_run(seq, 1e-3, n, cfg, mutation="improved<", variant="holdout", qs=qs)
+    I.check_loop_log(want, want, "unmutated")
+    assert _fails(lambda: I.check_loop_log(got, want, "strict"))
+
+
+MOVED = [(v, k) for v, table in (("holdout", I.HOLDOUT_SCRIPTS), ("ema", I.EMA_SCRIPTS), ("ema-holdout", I.EMA_SCRIPTS)) for k in sorted(table)]
+
+
+@pytest.mark.parametrize("variant, name", MOVED, ids=["%s-%s" % c for c in MOVED])
+def test_loop_model_variants_against_the_eager_rules(variant, name):
+    """The extended model against utils.select_latest_min + utils.EarlyStopping + the plateau arithmetic (iteration_cases.eager_loop_model)
+    on every script of the two shared tables: improved, best_iter, the lr each iteration used (bit-equal: both cut in fp32) and the
+    stopping iteration."""
+    rows, plateau, es = (I.HOLDOUT_SCRIPTS if variant == "holdout" else I.EMA_SCRIPTS)[name]
+    losses, qs, cfg, n = I.variant_scripts(variant)[name]
+    assert cfg == I.script_cfg(plateau, es) and n == len(rows)
+    ref = I.eager_loop_model(rows, 1e-3, plateau, es)
+    log, hist = I.loop_control_run(losses, 1e-3, n, cfg, variant=variant, qs=qs)
+    assert len(log) == len(ref)                                                # the stopping iteration
+    assert (log[-1][1] == 0) == (len(ref) < len(rows))
+    assert [r[0] for r in log] == [r[0] for r in ref]
+    assert [int(r[3][9]) for r in log] == [r[2] for r in ref]
+    lr_used = hist.reshape(n, -1)[:len(log), 3]
+    np.testing.assert_array_equal(lr_used, [r[1] for r in ref])
+    assert log[-1][3][0] == len(log) and np.isnan(hist.reshape(n, -1)[len(log):]).all()
+
+
+# ---- csrc/loop_rule.h as a stand-alone program -----------------------------------------------------------------------------------------
+def _hex64(x):
+    return "%016x" % int(np.float64(x).view(np.uint64))
+
+
+def test_loop_rule_header_as_plain_cpp_against_the_model(tmp_path):
+    """csrc/loop_rule.h, the one body behind the three dpi_loop_control* kernels, compiled as plain C++ with tests/host_loop_rule/main.cpp
+    under the address and undefined-behaviour sanitizers and run on the CPU over every script of every variant (variant_scripts: the
+    past-the-end case has six calls on a history of three rows), on heap buffers of exactly the documented sizes.  *improved, *active,
+    the bits of step_lr[1], every state double and the whole history must equal the numpy model's bit for bit, a NaN equal to a NaN.
+    The sanitizers instrument host code only: nothing here is compiled for, or run on, a device."""
+    import os
+    import shutil
+    import subprocess
+    from conftest import ROOT
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    csrc = os.path.join(ROOT, "deep_prior_interpolation_amd", "csrc")
+    exe = str(tmp_path / "host_loop_rule")
+    flags = ("-x c++ -O1 -g -std=c++17 -ffp-contract=off -Wall -Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined "
+             "-fno-omit-frame-pointer")
+    subprocess.check_call([hipcc] + flags.split() + ["-I", csrc, os.path.join(ROOT, "tests", "host_loop_rule", "main.cpp"), "-o", exe], timeout=300)
+    cases, lines = [], []
+    for variant, (ho, ema) in I.LOOP_VARIANTS.items():
+        for name, (losses, qs, cfg, n) in sorted(I.variant_scripts(variant).items()):
+            cases.append((variant, name, I.loop_control_run(losses, 1e-3, n, cfg, variant=variant, qs=qs)))
+            n_in = 11 if ho else 8
+            lines.append("run %d %d %d %d %d %08x %d %s %s %d %s %s %d %s" % (
+                ho, ema, n, len(losses), n_in, int(F(1e-3).view(np.uint32)), cfg["use_plateau"], _hex64(cfg["factor"]), _hex64(cfg["threshold"]),
+                cfg["patience"], _hex64(cfg["min_lr"]), _hex64(cfg["lr_eps"]), cfg["es_patience"], _hex64(cfg["es_min_delta"])))
+            for it, loss in enumerate(losses):
+                for x in I.loop_inputs(variant, it, loss, None if qs is None else qs[it]):
+                    if x is not None:
+                        lines.append(" ".join(_hex64(v) for v in x[:n_in]))
+    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    out = r.stdout.split("\n")
+    assert out[-2] == "%d runs" % len(cases) and len(cases) == 10 + (4 + 1) + 2 * (5 + 1)
+    doubles = lambda words: np.array([int(w, 16) for w in words], dtype=np.uint64).view(np.float64)
+    k = 0
+    for variant, name, (want, want_hist) in cases:
+        got = []
+        while out[k].startswith("C "):
+            w = out[k].split()
+            got.append((int(w[1]), int(w[2]), float(np.array([int(w[3], 16)], dtype=np.uint32).view(F)[0]), doubles(w[4:])))
+            k += 1
+        assert out[k].startswith("H")
+        got_hist = doubles(out[k].split()[1:])
+        k += 1
+        what = "loop_rule.h %s %s" % (variant, name)
+        I.check_loop_log(got, want, what)
+        for g, w in zip(got, want):                                             # bit patterns, beyond check_loop_log's values
+            same = (g[3].view(np.uint64) == w[3].view(np.uint64)) | (np.isnan(g[3]) & np.isnan(w[3]))
+            assert same.all(), (what, g[3], w[3])
+        assert got_hist.shape == want_hist.shape, what
+        same = (got_hist.view(np.uint64) == want_hist.view(np.uint64)) | (np.isnan(got_hist) & np.isnan(want_hist))
+        assert same.all(), (what, got_hist, want_hist)
+
+
 @pytest.mark.parametrize("name", [k for k in I.OVERLAP_CASES if not k.startswith("65")])
 def test_a_window_count_with_kmax_off_by_one_fails_the_check(name):
     volume, patch, stride, _ = I.OVERLAP_CASES[name]
