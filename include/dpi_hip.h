@@ -214,7 +214,10 @@ int dpi_bn_bwd_apply(const float* dy, const float* x, const float* mean_invstd, 
                      float* dbeta, void* stream);
 /* dpi_bn_bwd_apply fused with phase 1 (dpi_bn_bwd_reduce) of up to two BatchNorms whose incoming gradient is this dx
  * (the residual joins of Block3d / ResPath3d, mulresunet.py:92-94,109-111): partials_a/b[dpi_stat_blocks][C][2] receive
- * {sum g, sum g*xhat} of dx against (xa, mi_a, gamma_a, beta_a, chain_a, post_a) resp. (xb, ...); xa / xb may be NULL. */
+ * {sum g, sum g*xhat} of dx against (xa, mi_a, gamma_a, beta_a, chain_a, post_a) resp. (xb, ...); xa / xb may be NULL.
+ * Rows: `partials` is read as nblk rows [nblk][C][2], whatever wrote them (nblk is the caller's, not dpi_stat_blocks); partials_a / _b are
+ * WRITTEN as dpi_stat_blocks(C, V) rows each, every row, and only where that side's x is given; they describe the dx the launch stored (the
+ * bf16-rounded one with DPI_STORE_GRAD_BF16).  dgamma / dbeta may be NULL.  tests/test_gpu_join_contract.py holds all of this. */
 int dpi_bn_bwd_apply_fork(const float* dy, const float* x, const float* mean_invstd, const float* gamma,
                           const float* beta, const float* in_chain, float pre_slope, float post_slope,
                           const double* partials, int nblk, int C, size_t V, float* dx, float* dgamma,
@@ -224,7 +227,11 @@ int dpi_bn_bwd_apply_fork(const float* dy, const float* x, const float* mean_inv
                           const float* chain_b, float post_b, double* partials_b, void* stream);
 /* Phase 2 of TWO BatchNorm backward passes that share the incoming gradient dy (the two branches of a residual join), from
  * their phase-1 partials, in one pass; optionally phase 1 of one more BatchNorm whose incoming gradient is dxb on the
- * channels [f_lo, f_hi) and whose input is xb itself (raw): f_partials[dpi_stat_blocks][f_hi - f_lo][2]. */
+ * channels [f_lo, f_hi) and whose input is xb itself (raw): f_partials[dpi_stat_blocks][f_hi - f_lo][2].
+ * Rows: partials_a / partials_b are read as nblk rows [nblk][C][2] each (the caller's count); f_partials is WRITTEN as
+ * dpi_stat_blocks(C, V) rows of f_hi - f_lo channels, every row, and describes the stored dxb.  dxa and dxb are written on every channel,
+ * the fork range of dxb included.  f_partials == NULL: no fork, f_lo / f_hi and the f_* tables are not looked at; f_partials != NULL
+ * requires 0 <= f_lo < f_hi <= C and f_mi. */
 int dpi_bn_bwd_apply_dual(const float* dy, int nblk, int C, size_t V, const float* xa, const float* mi_a,
                           const float* gamma_a, const float* beta_a, const float* chain_a, float post_a,
                           const double* partials_a, float* dxa, float* dgamma_a, float* dbeta_a, const float* xb,
@@ -688,7 +695,13 @@ int dpi_pocs_project(const float* x, const float* wdata, const float* wmask, siz
  * call computes on the widened operands.
  * ws: dpi_join_bwd_ws_doubles(C, V) doubles; coef: C x 8 floats of scratch (the per-channel constants the apply pass reads).
  * mi* = {mean[C], invstd[C]} as dpi_bn_finalize wrote them; post_* = slope of the activation BEHIND that BatchNorm (1 = none);
- * pre = slope of the activation in FRONT of the top BatchNorm.  t may be NULL (see dpi_chain_add_apply below). */
+ * pre = slope of the activation in FRONT of the top BatchNorm.  t may be NULL (see dpi_chain_add_apply below).
+ * What a launch writes (tests/test_gpu_join_contract.py): every element of dxa, of dxf [f_hi - f_lo][V], of coef [C][8] (the fork's pair
+ * {f1, f2} = 0 off the fork range), of dgb [6][C] and of dgb_f [2][f_hi - f_lo]; dxb on the channels OUTSIDE [f_lo, f_hi) only — the fork
+ * channels of dxb are not touched, their result is dxf; ws up to dpi_join_bwd_ws_doubles(C, V) = dpi_stat_blocks(C, V) * C * 24 doubles and
+ * not beyond.  gamma / beta of any of the four BatchNorms may be NULL (= 1, 0).  f_lo == f_hi (0 <= f_lo <= C): no fork, and f_mi, f_gamma,
+ * f_beta, dxf, dgb_f are not dereferenced (may be NULL).  Refused (DPI_E_ARG): f_lo < 0, f_hi > C, f_lo > f_hi, a non-empty fork without
+ * f_mi / dxf / dgb_f, t == NULL without both forward chains, unknown io bits, C <= 0, V == 0, any other pointer NULL. */
 size_t dpi_join_bwd_ws_doubles(int C, size_t V);
 int dpi_join_bwd(const float* dy, const float* t, const float* mi, const float* gamma, const float* beta, float pre, int C, size_t V,
                  const float* xa, const float* mi_a, const float* gamma_a, const float* beta_a, const float* chain_a, float post_a,

@@ -91,6 +91,8 @@ def v_problem(V, bf16):
     p["chain"], p["chain_out"] = E.chain_table(3, gen), E.chain_table(3, gen, identity=(2,))
     p["gamma"], p["beta"] = torch.rand(3, generator=gen) + 0.5, torch.randn(3, generator=gen) * 0.3
     p["chain_d"], p["chain_out_d"] = p["chain"].to(DEV), p["chain_out"].to(DEV)          # held here: a temporary would be freed before the launch
+    p["chain_b"] = E.chain_table(3, gen, identity=(0,))                                    # drawn last: the operands above keep their values
+    p["chain_b_d"] = p["chain_b"].to(DEV)
     return p
 
 
@@ -186,21 +188,16 @@ def test_bn_bwd_reduce_and_apply(lib, row, io, form):
     assert rel(dgg.payload, dg) < 2e-4 and rel(dbg.payload, db) < 2e-4, (rel(dgg.payload, dg), rel(dbg.payload, db))
 
 
-@pytest.mark.parametrize("store_t", [True, False], ids=["t", "stats-only"])
-@v_io
-def test_chain_add_stats(lib, row, io, store_t):
-    """t = T_a(a) + b (chain_b NULL) and the partial rows of act(t).  k = 8 for the sums, 10 for the squares, terms mag(T_a(a)) + |b|: three
-    roundings in T_a, one in the sum, one in the slope product (5), three pre-sum additions; squares 2 x 5, summed in double.  With t stored
-    as bf16 the statistics describe the STORED t: they are held against float64 sums of act(what the launch stored) — k = 4 and 2: the slope
-    product and the pre-sum."""
+def _chain_add_stats(lib, row, io, store_t, with_chain_b):
     L, p = lib.load(), v_problem(row.V, bool(io))
     C_, V = 3, row.V
+    chain_b, chain_b_d = (p["chain_b"], p["chain_b_d"]) if with_chain_b else (None, None)
     ag, bg = gin(p["a"], dt(io, 1)), gin(p["b"], dt(io, 1))
     tg, pg = (gout(C_, V, dt(io, 1)) if store_t else None), gvec(row.nblk * C_ * 2, F64)
-    _launch(lib, L.dpi_chain_add_stats_io(ptr(ag), ptr(p["chain_d"]), ptr(bg), None, C_, V, S02, ptr(tg), ptr(pg), io & 1, lib.stream()),
+    _launch(lib, L.dpi_chain_add_stats_io(ptr(ag), ptr(p["chain_d"]), ptr(bg), ptr(chain_b_d), C_, V, S02, ptr(tg), ptr(pg), io & 1, lib.stream()),
             "dpi_chain_add_stats_io")
     _check_guards([("a", ag), ("b", bg), ("t", tg), ("partials", pg)], "chain_add_stats " + vid(row))
-    t64 = E.chain_add64(p["a"], p["chain"], p["b"], None)
+    t64 = E.chain_add64(p["a"], p["chain"], p["b"], chain_b)
     got = pg.payload.view(row.nblk, C_, 2)
     if store_t:
         stored_ok(tg.payload, t64, "t", 5e-6)
@@ -208,18 +205,47 @@ def test_chain_add_stats(lib, row, io, store_t):
         y = E.lrelu(tg.payload.float().cpu().double(), S02)
         E.check_partials(got, E.partials64(y), stat_mags(y.abs()), torch.tensor([4.0, 2.0], dtype=F64), "chain_add_stats (stored t) " + vid(row))
     else:
-        mag = E.chain_mag64(p["a"], p["chain"]) + p["b"].double().abs()
+        mag = E.chain_mag64(p["a"], p["chain"]) + E.chain_mag64(p["b"], chain_b)
         E.check_partials(got, E.partials64(E.lrelu(t64, S02)), stat_mags(mag), torch.tensor([8.0, 10.0], dtype=F64), "chain_add_stats " + vid(row))
+
+
+@pytest.mark.parametrize("store_t", [True, False], ids=["t", "stats-only"])
+@v_io
+def test_chain_add_stats(lib, row, io, store_t):
+    """t = T_a(a) + b (chain_b NULL) and the partial rows of act(t).  k = 8 for the sums, 10 for the squares, terms mag(T_a(a)) + |b|: three
+    roundings in T_a, one in the sum, one in the slope product (5), three pre-sum additions; squares 2 x 5, summed in double.  With t stored
+    as bf16 the statistics describe the STORED t: they are held against float64 sums of act(what the launch stored) — k = 4 and 2: the slope
+    product and the pre-sum."""
+    _chain_add_stats(lib, row, io, store_t, False)
+
+
+@pytest.mark.parametrize("store_t", [True, False], ids=["t", "stats-only"])
+@v_io
+def test_chain_add_stats_with_chain_b(lib, row, io, store_t):
+    """t = T_a(a) + T_b(b), what side B of a Block3d join carries (channel 0 of chain_b is the identity).  The same k: T_b's three roundings
+    are at most 3 x 2^-24 of mag(T_b(b)) as T_a's are of mag(T_a(a)), so the terms mag(T_a(a)) + mag(T_b(b)) keep k = 8 and 10."""
+    _chain_add_stats(lib, row, io, store_t, True)
+
+
+def _chain_add_apply(lib, row, io, with_chain_b):
+    L, p = lib.load(), v_problem(row.V, bool(io))
+    chain_b, chain_b_d = (p["chain_b"], p["chain_b_d"]) if with_chain_b else (None, None)
+    ag, bg, yg = gin(p["a"], dt(io, 1)), gin(p["b"], dt(io, 1)), gout(3, row.V, dt(io, 1))
+    _launch(lib, L.dpi_chain_add_apply(ptr(ag), ptr(p["chain_d"]), ptr(bg), ptr(chain_b_d), ptr(p["chain_out_d"]), 3, row.V, ptr(yg), io & 1, lib.stream()),
+            "dpi_chain_add_apply")
+    _check_guards([("a", ag), ("b", bg), ("y", yg)], "chain_add_apply " + vid(row))
+    stored_ok(yg.payload, E.chain64(E.chain_add64(p["a"], p["chain"], p["b"], chain_b), p["chain_out"]), "chain_add_apply y", 5e-6)
 
 
 @v_io
 def test_chain_add_apply(lib, row, io):
-    L, p = lib.load(), v_problem(row.V, bool(io))
-    ag, bg, yg = gin(p["a"], dt(io, 1)), gin(p["b"], dt(io, 1)), gout(3, row.V, dt(io, 1))
-    _launch(lib, L.dpi_chain_add_apply(ptr(ag), ptr(p["chain_d"]), ptr(bg), None, ptr(p["chain_out_d"]), 3, row.V, ptr(yg), io & 1, lib.stream()),
-            "dpi_chain_add_apply")
-    _check_guards([("a", ag), ("b", bg), ("y", yg)], "chain_add_apply " + vid(row))
-    stored_ok(yg.payload, E.chain64(E.chain_add64(p["a"], p["chain"], p["b"], None), p["chain_out"]), "chain_add_apply y", 5e-6)
+    _chain_add_apply(lib, row, io, False)
+
+
+@v_io
+def test_chain_add_apply_with_chain_b(lib, row, io):
+    """chain_b != NULL: y = T_out(T_a(a) + T_b(b)), the same 5e-6."""
+    _chain_add_apply(lib, row, io, True)
 
 
 # ---- partial-row counts ------------------------------------------------------------------------------------------------------------------
