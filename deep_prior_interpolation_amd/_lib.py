@@ -133,6 +133,10 @@ SIGNATURES = {
     # library fails on the unresolved symbols
     "dpi_avo_fwd": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
     "dpi_avo_adj": (_I, [_P, _P, _I, _I, _Z, _P, _P]),
+    # --wavelet, operators/signal.py:8-45 behind operators/derivative.py:8-21: (m, taps, K, diff, C, T, S, d, stream) and
+    # (d, taps, K, diff, C, T, S, m, stream).  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_wavelet_fwd": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P]),
+    "dpi_wavelet_adj": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P]),
     # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

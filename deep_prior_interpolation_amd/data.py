@@ -6,7 +6,8 @@ unsorted glob, data.py:99 — SURVEY App. B.7).
 
 Ours, opt-in: --reassembly cover cuts (and re-assembles) one more, edge-flush window on every axis the regular grid leaves a tail on, --blend
 taper weights the overlaps (utils/patch_extractor.py); `reconstruct_patches(field="posterior_std")` blends the per-patch spread of a sampler run,
-`reconstruct_patches(field="avo_model")` re-assembles the three parameter sections of an --avo_theta run."""
+`reconstruct_patches(field="avo_model")` re-assembles the three parameter sections of an --avo_theta run,
+`reconstruct_patches(field="wavelet_model")` the section behind the outputs of a --wavelet run."""
 import os
 from glob import glob
 from typing import List
@@ -167,9 +168,11 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     sqrt(sum(w sigma^2) / sum(w)) / |gain|, a patch without one (skipped, or fewer than two samples) counting as 0.  --reassembly cover
     returns the input's shape, --blend taper weights the overlaps; with the defaults and field = "output" nothing differs from before.
     field = "avo_model" (an --avo_theta run) re-assembles the per-patch parameter sections (T, X, 3) into (T', X', 3) with the same windows
-    and weights along t and x, divided by gain (the model is linear in the data); a skipped patch counts as zeros."""
-    if field not in ("output", "posterior_std", "avo_model"):
-        raise ValueError("field must be output, posterior_std or avo_model, got %r" % (field,))
+    and weights along t and x, divided by gain (the model is linear in the data); a skipped patch counts as zeros.
+    field = "wavelet_model" (a --wavelet run) re-assembles the per-patch sections behind the outputs exactly like the outputs: same windows,
+    same weights, divided by gain; a patch without one (skipped) counts as zeros."""
+    if field not in ("output", "posterior_std", "avo_model", "wavelet_model"):
+        raise ValueError("field must be output, posterior_std, avo_model or wavelet_model, got %r" % (field,))
     if field == "avo_model":
         return _reconstruct_avo_model(args, results_root)
     cover, blend = reassembly_flags(args)
@@ -183,6 +186,8 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     outs, elapsed, history, dev = [], [], [], "?"
     for path in files:
         rec = np.load(path, allow_pickle=True).item()
+        if field == "wavelet_model" and "wavelet" not in rec:
+            raise ValueError("%s holds no wavelet_model: not the result of a --wavelet run" % path)
         v = rec["output"] if field == "output" else rec.get(field)
         outs.append(np.asarray(v) if v is not None else np.zeros_like(np.asarray(rec["output"])))
         elapsed.append(rec.get("elapsed", rec.get("elapsed time")))
@@ -193,12 +198,13 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     patches_out = np.asarray(outs)
     if args.datadim == "2.5d":
         patches_out = transpose_patches_25d(patches_out, args.slice, adj=True)
-    if not cover and blend == "flat" and field == "output":
+    linear = field in ("output", "wavelet_model")          # blended like the data and divided by gain; else a spread
+    if not cover and blend == "flat" and linear:
         outputs = pe.reconstruct(patches_out.reshape(pa_shape)) / args.gain
     else:
         origins = u.window_origins(inputs.shape, pe.dim, pe.stride, cover=cover)
         outputs = u.reassemble(patches_out.reshape((-1,) + pe.dim), origins, u.reassembled_shape(inputs.shape, pe.dim, pe.stride, cover),
-                               pe.dim, pe.stride, blend, spread=field != "output") / (args.gain if field == "output" else abs(args.gain))
+                               pe.dim, pe.stride, blend, spread=not linear) / (args.gain if linear else abs(args.gain))
     if verbose:
         print("\n%d patches; total elapsed time on %s: %s"
               % (len(history), dev, u.sec2time(sum(u.time2sec(e) for e in elapsed if e))))

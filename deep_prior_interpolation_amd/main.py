@@ -17,7 +17,7 @@ from .architectures import build_net
 from .data import extract_patches
 from .loop import LoopRule
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import check_avo, check_out_ema, check_trace_offsets_flag, net_args_are_same, parse_arguments
+from .parameter import check_avo, check_out_ema, check_trace_offsets_flag, check_wavelet, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -49,6 +49,11 @@ class Interpolator:
         # --avo_theta (ours): the net outputs three elastic-parameter sections, the AVO operator maps them to the angle sections (net_forward)
         self.avo = check_avo(args)                               # None, or (theta, vsvp, linearization)
         self._avo_op = None                                      # built per patch length T (net_forward)
+        # --wavelet (ours): the net writes a reflectivity / log-impedance section, the wavelet operator behind it (and behind the AVO
+        # operator) maps it to the traces (net_forward); the section behind the selected output is kept on the device
+        self.wavelet = check_wavelet(args)                       # None, or (file name, kind)
+        self._wavelet_op = self._load_wavelet()
+        self._wavelet_pre = self._wavelet_best = None            # the operator's input of this iteration / of the selected iterate
         # --trace_offsets (ours): the loss sees the grid output sampled at the recorded trace positions (data_forward)
         self.trace_offsets_file = check_trace_offsets_flag(args)
         self.trace_interp = getattr(args, "trace_interp", None) or "linear"     # --trace_interp: the kernel R samples with (linear = bilinear)
@@ -108,6 +113,31 @@ class Interpolator:
         self.holdout_sel = self._holdout_dev = None
         self._load_trace_offsets(data.get("offsets"))
         return torch.std(self.img_ * self.mask_).item()
+
+    def _load_wavelet(self):
+        """--wavelet: the file in --imgdir -> the operator, its taps on the device before iteration 0 (a captured iteration replays it
+        unchanged).  None when the flag is off."""
+        if self.wavelet is None:
+            return None
+        name, kind = self.wavelet
+        from .operators import ConvolutionalModelling
+        path = os.path.join(self.args.imgdir, name)
+        try:
+            op = ConvolutionalModelling(np.load(path, allow_pickle=False), kind=kind)
+        except (OSError, ValueError) as e:
+            raise ValueError("--wavelet %s: %s" % (path, e)) from e
+        if self.device.type == "cuda":
+            op.upload(self.device)
+        return op
+
+    def wavelet_model(self):
+        """--wavelet: the section behind the selected output — the operator's input at the selected iteration, i.e. the reflectivity or
+        log-impedance section (behind --avo_theta: the angle sections before the wavelet) — in the numpy order and shape of `output`, in
+        the patch's gained units.  None for a patch that was not optimised, and with --out_ema or a sampler: the selected output there is
+        an average of iterates whose model is not tracked."""
+        if self._wavelet_op is None or self._wavelet_best is None or self.out_ema > 0.0 or self.is_sampler():
+            return None
+        return self._to_numpy_out(self._wavelet_best)
 
     def _load_trace_offsets(self, offsets):
         """--trace_offsets: the patch's (X, Y, 2) offsets -> the sampling operator behind the network's output (data_forward).  Offsets of
@@ -284,10 +314,15 @@ class Interpolator:
         main.py:159, which its PartialUNet.forward(x, mask) cannot serve): training_mask(), so held-out traces are holes for the net too, as one
         channel (amax over dim 1: the 2.5-D slab's channels; in 3-D the mask itself).  Constant per patch: built once, so a captured
         iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
-        them to the patch's angle sections: what this returns is a data-domain tensor either way."""
+        them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m): what this returns is a data-domain
+        tensor either way."""
+        out = self._net_forward(z)
         if self.avo is not None:
-            return self._avo_operator(int(z.shape[2]))(self._net_forward(z))
-        return self._net_forward(z)
+            out = self._avo_operator(int(z.shape[2]))(out)
+        if self._wavelet_op is not None:
+            self._wavelet_pre = out.detach()                     # kept when this iterate is selected (wavelet_model)
+            out = self._wavelet_op(out)
+        return out
 
     def _avo_operator(self, nt0):
         """--avo_theta: the operator of the loaded patch (nt0 = its T), built once and kept while T stays the same; its coefficients are
@@ -540,6 +575,8 @@ class Interpolator:
             self._out_best_dev = self._ema_best
         elif improved:
             self._out_best_dev = out_.detach()       # stays on the GPU; copied to the host once, after the loop
+            if self._wavelet_op is not None:
+                self._wavelet_best = self._wavelet_pre                   # W is not invertible: the section behind it is kept beside it
         if self.iiter in self.iter_to_be_saved and self.iiter != 0:
             np.save(os.path.join(self.outpath, self.image_name.split(".")[0]
                                  + "_output%s.npy" % str(self.iiter).zfill(self.zfill)), self._to_numpy_out(out_))
@@ -703,7 +740,7 @@ class Interpolator:
         self._ensure_holdout()
         rule = self._g_rule = self.loop_rule()
         self._g_state, self._g_hist, self._g_improved = rule.new_state(a.epochs, dev)
-        self._g_best = None
+        self._g_best = self._g_wbest = None
 
         def one_iteration():
             with self.precision_scope():
@@ -724,6 +761,13 @@ class Interpolator:
             best_src = self._ema_avg if rule.ema else out_       # --out_ema: the selected AVERAGE is kept
             _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(best_src), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
+            if self._wavelet_op is not None and not rule.ema:
+                # --wavelet: the section behind the selected iterate, on the same flag, into a buffer of its own
+                pre = self._wavelet_pre
+                if self._g_wbest is None:
+                    self._g_wbest = torch.empty_like(pre)
+                _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(pre), _lib.ptr(self._g_wbest), pre.numel(),
+                                         _lib.stream()), "dpi_copy_if")
 
         one_iteration()                                  # iteration 0, eager (also warms every lazy cache)
         if quiet_device:
@@ -756,6 +800,7 @@ class Interpolator:
         self._g_rule.fill(self, self.history, h, st)
         self.iiter = n
         self._out_best_dev = self._g_best
+        self._wavelet_best = self._g_wbest
         self.out_best = self._to_numpy_out(self._g_best)
         self._finish_posterior()
 
@@ -806,6 +851,9 @@ class Interpolator:
             run["best_iter"] = self.best_iter
         if self.avo is not None:
             run.update(avo_theta=list(self.avo[0]), avo_vsvp=self.avo[1], avo_linearization=self.avo[2], avo_model=self.avo_model())
+        if self._wavelet_op is not None:
+            # the taps as used (w, or w / 2 for impedance) and the section behind `output`; None: see wavelet_model()
+            run.update(wavelet=self._wavelet_op.taps.copy(), wavelet_model_kind=self._wavelet_op.kind, wavelet_model=self.wavelet_model())
         if self.trace_offsets_file is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
             run["trace_interp"] = self.trace_interp
@@ -821,6 +869,7 @@ class Interpolator:
         self.loss_min = None
         self.best_iter = self.val_min = self.ema_min = None
         self._out_best_dev = None
+        self._wavelet_pre = self._wavelet_best = None            # the section behind the output belongs to the patch
         self._ema_avg = self._ema_best = None                    # the running average belongs to the patch
         self._reset_posterior()
         self._zero_moments()

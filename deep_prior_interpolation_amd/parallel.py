@@ -604,9 +604,19 @@ def main(argv=None):
             volumes["std"] = reconstruct_patches(args, field="posterior_std")
         if rank == 0 and getattr(args, "avo_theta", None) is not None:
             volumes["avo"] = reconstruct_patches(args, field="avo_model")
+    if getattr(args, "wavelet", None) is not None and not sampler and not (getattr(args, "out_ema", 0.0) or 0.0):
+        # --wavelet: the section behind reconstructed.npy, re-assembled on the host from the result files of every rank with the same
+        # windows and weights (--out_ema and the samplers track no model: nothing to re-assemble)
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            from .data import reconstruct_patches
+            volumes["model"] = reconstruct_patches(args, field="wavelet_model")
     _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
+        if volumes.get("model") is not None:
+            np.save(os.path.join(outpath, "reconstructed_model.npy"), volumes["model"])
         if sampler and volumes.get("std") is not None:
             # the window-weighted mean of the per-patch posterior variances, as a std: the spread WITHIN the windows
             np.save(os.path.join(outpath, "reconstructed_std.npy"), volumes["std"])

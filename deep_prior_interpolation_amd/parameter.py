@@ -140,6 +140,15 @@ _FLAGS = [
                               help="ours: how --trace_offsets samples the grid output at the recorded positions: linear = 2 taps per axis "
                                    "(bilinear), cubic = 4 taps (Keys, a = -1/2), sinc8 = 8 taps (Kaiser-windowed sinc).  The wider kernels "
                                    "keep more of the spatial wavenumbers close to aliasing; needs --trace_offsets")),
+    # convolutional modelling (ours: the reference ships operators/signal.py VerticalConv and operators/derivative.py VerticalGrad without a caller)
+    (("--wavelet",), dict(type=str, required=False,
+                         help="ours: a .npy in --imgdir with a known wavelet, 1-D, odd length <= 255, centre sample = time zero (absent = off).  "
+                              "The network then writes the section behind the traces and the wavelet maps it to what the loss sees, so every "
+                              "output is confined to the wavelet's band along t; the section is saved as wavelet_model.  Time must be dim 2 of "
+                              "the device tensor: --datadim 2d, 3d, or 2.5d with --slice tx | ty")),
+    (("--wavelet_model",), dict(type=str, required=False, default="reflectivity", choices=["reflectivity", "impedance"],
+                               help="ours: what the network writes under --wavelet: reflectivity = r, traces d = w * r; impedance = m = ln(AI), "
+                                    "traces d = 0.5 w * D m with D the forward difference along t; needs --wavelet")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -179,6 +188,7 @@ def postprocess(args: Namespace) -> Namespace:
     check_out_ema(args)
     check_trace_offsets_flag(args)
     check_avo(args)
+    check_wavelet(args)
     return args
 
 
@@ -206,6 +216,26 @@ def check_trace_offsets_flag(args: Namespace):
         raise ValueError("--trace_offsets does not combine with --optimizer %s: the misfit of the posterior mean is evaluated on the grid, "
                          "not at the recorded positions" % args.optimizer)
     return name
+
+
+def check_wavelet(args: Namespace):
+    """--wavelet and what it needs; returns None when it is off (also for a Namespace without the keys, as those of older args.txt files),
+    else (file name, kind).  The file itself is read and checked where the operator is built (main.Interpolator)."""
+    name = getattr(args, "wavelet", None)
+    kind = getattr(args, "wavelet_model", None) or "reflectivity"
+    if kind not in ("reflectivity", "impedance"):
+        raise ValueError("--wavelet_model must be reflectivity or impedance, got %r" % (kind,))
+    if name is None:
+        if kind != "reflectivity":
+            raise ValueError("--wavelet_model %s needs --wavelet: without a wavelet nothing is modelled and the flag would silently do "
+                             "nothing" % kind)
+        return None
+    # the operator filters along dim 2 of the device tensor (1, C, T, ...): data.transpose_patches_25d leaves t there for the tx slabs
+    # (T, X, Y-as-channels) and the ty slabs (T, Y, X-as-channels); the xy slabs are (X, Y, T-as-channels)
+    if args.datadim == "2.5d" and args.slice not in ("tx", "ty"):
+        raise ValueError("--wavelet needs the time axis as dim 2 of the patch: --datadim 2d, 3d, or 2.5d with --slice tx or ty; "
+                         "--slice %s stacks t into the channels" % args.slice)
+    return name, kind
 
 
 def check_avo(args: Namespace):
@@ -301,6 +331,11 @@ def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
     # --trace_interp (ours) decides the operator the weights were fitted through; an args.txt without the key: linear
     if (a.get("trace_interp") or "linear") != (b.get("trace_interp") or "linear"):
         errors.append("trace_interp")
+    # --wavelet / --wavelet_model (ours) decide what the network's output means; an args.txt without the keys: off / reflectivity
+    if a.get("wavelet") != b.get("wavelet"):
+        errors.append("wavelet")
+    if (a.get("wavelet_model") or "reflectivity") != (b.get("wavelet_model") or "reflectivity"):
+        errors.append("wavelet_model")
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

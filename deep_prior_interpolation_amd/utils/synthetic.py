@@ -16,7 +16,7 @@ bench patch): kept because committed reference recordings (`tests/golden/plateau
 import numpy as np
 
 __all__ = ["hyperbolic_volume", "tiled_hyperbolic_volume", "sparse_hyperbolic_volume", "random_trace_mask", "coarse_std", "avo_gathers",
-           "hyperbolic_traces"]
+           "hyperbolic_traces", "ricker"]
 
 TARGET_RMS = 0.19          # std of the un-gained cube: 40 * 0.19 * sqrt(0.34) = 4.4, the middle of the notebook's 3.94 .. 5.16
 
@@ -136,6 +136,20 @@ def hyperbolic_traces(shape, offsets, seed=0, dtype=np.float32):
         t0 += rng.uniform(18.0, 32.0) * s
     rec *= TARGET_RMS / max(float(grid.std()), 1e-12)
     return rec.astype(dtype)
+
+
+def ricker(f0, dt, K, dtype=np.float64):
+    """Ricker wavelet of peak frequency f0 (Hz) sampled every dt (s) on K samples (odd) centred on time zero:
+    w(t) = (1 - 2 a) exp(-a), a = (pi f0 t)^2 — symmetric, 1 at the centre sample.  The wavelet of `hyperbolic_volume` is
+    ricker(0.055 / s, 1, K) (f0 in cycles per sample)."""
+    K = int(K)
+    if K < 1 or K % 2 == 0:
+        raise ValueError("ricker: K must be odd and >= 1, got %r" % (K,))
+    if not (f0 > 0 and dt > 0):
+        raise ValueError("ricker: f0 and dt must be > 0, got %r, %r" % (f0, dt))
+    t = (np.arange(K, dtype=np.float64) - K // 2) * float(dt)
+    a = (np.pi * float(f0) * t) ** 2
+    return ((1.0 - 2.0 * a) * np.exp(-a)).astype(dtype)
 
 
 def random_trace_mask(shape, rate, seed=0, dtype=np.float32):

@@ -622,6 +622,23 @@ int dpi_structure_tensor_sections(const float* x, int C, int T, int X, int Y, fl
 int dpi_avo_fwd(const float* x, const float* G, int ntheta, int T, size_t S, float* y, void* stream);
 int dpi_avo_adj(const float* y, const float* G, int ntheta, int T, size_t S, float* x, void* stream);
 
+/* ---------------------------------------------------------------- Convolutional modelling (--wavelet) --
+ * Replaces operators/signal.py:8-45 (VerticalConv: every trace convolved with a wavelet along t) behind operators/derivative.py:8-21
+ * (VerticalGrad: the forward difference along t, last row zero) in one launch each way: the convolutional model of seismic data,
+ * d = w * r on a reflectivity section (diff = 0) and d = (w / 2) * D ln(AI) on a log-impedance section (diff = 1, taps = w / 2).
+ * Tensors [C][T][S] fp32, contiguous, S = X or X * Y: one layout for (1, C, T, X) and (1, C, T, X, Y).  taps: K floats on the device.
+ *     dpi_wavelet_fwd:  d[c][t][s] = sum_k taps[k] * u[c][t + K/2 - k][s], zero outside [0, T): a true convolution centred on K/2, the
+ *                       arithmetic of dpi_fir_axis0.  diff = 0: u = m.  diff = 1: u[t] = m[t + 1] - m[t] for t < T - 1, u[T - 1] = 0.
+ *     dpi_wavelet_adj:  the exact transpose: g[t] = sum_k taps[k] * d[t - K/2 + k]; diff = 0: m = g; diff = 1:
+ *                       m[t] = -g[t] [t < T - 1] + g[t - 1] [t >= 1].
+ * Every sum is one fmaf chain from 0 over the taps in ascending k (the adjoint: over its reversed taps), whatever the tile or the
+ * length of the wavelet; the difference is rounded once.  K odd, 1 <= K <= 255; T < K/2 is fine (a wavelet longer than the trace).
+ * Any 4-byte aligned tensors: the input is read 16 bytes at a time when S % 4 == 0 and it starts on 16 bytes, one element at a time
+ * otherwise, with the same bits either way.  Null or aliased pointers, an even K or one out of range, diff other than 0 / 1 and
+ * C, T, S < 1 return an error before any launch.  ABI version stays: a stale library fails on the unresolved symbols. */
+int dpi_wavelet_fwd(const float* m, const float* taps, int K, int diff, int C, int T, size_t S, float* d, void* stream);
+int dpi_wavelet_adj(const float* d, const float* taps, int K, int diff, int C, int T, size_t S, float* m, void* stream);
+
 /* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
  * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
  * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]
