@@ -661,7 +661,8 @@ class Interpolator:
         tracking, plateau LR and early stopping live on the device (dpi_loop_control / dpi_copy_if), the host only polls
         the `active` flag every `check_every` replays.  Same arithmetic, same stopping iteration.
         "auto" picks "graph" unless per-iteration host work was requested (net_inputs, --save_every) or the patch has >= 2^20 voxels
-        (eager with the weight-gradient and branch streams).
+        (eager with the weight-gradient and branch streams).  A patch of that size that does not take those streams (--net part) is
+        eager only when the run is short: from 1000 iterations on it is captured.
         --holdout: out_best and early stopping follow the misfit on the held-out traces, ReduceLROnPlateau the training loss.
         --out_ema: out_best is the running average of the outputs at the iteration where ITS misfit (training, or held-out with --holdout)
         was lowest, and early stopping follows that misfit; the gradient and ReduceLROnPlateau see the raw iterate as ever."""
