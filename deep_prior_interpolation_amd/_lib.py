@@ -137,6 +137,10 @@ SIGNATURES = {
     # (d, taps, K, diff, C, T, S, m, stream).  ABI_VERSION stays: a stale library fails on the unresolved symbols
     "dpi_wavelet_fwd": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P]),
     "dpi_wavelet_adj": (_I, [_P, _P, _I, _I, _I, _I, _Z, _P, _P]),
+    # --moveout (ours): (m, tau, interp, C, T, S, d, stream) and (d, tau, range, interp, C, T, S, m, stream); tau = [T][S] fp32, range =
+    # [2][T][S] int32, interp 0 = linear, 1 = cubic.  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_moveout_fwd": (_I, [_P, _P, _I, _I, _I, _Z, _P, _P]),
+    "dpi_moveout_adj": (_I, [_P, _P, _P, _I, _I, _I, _Z, _P, _P]),
     # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -7,7 +7,8 @@ unsorted glob, data.py:99 — SURVEY App. B.7).
 Ours, opt-in: --reassembly cover cuts (and re-assembles) one more, edge-flush window on every axis the regular grid leaves a tail on, --blend
 taper weights the overlaps (utils/patch_extractor.py); `reconstruct_patches(field="posterior_std")` blends the per-patch spread of a sampler run,
 `reconstruct_patches(field="avo_model")` re-assembles the three parameter sections of an --avo_theta run,
-`reconstruct_patches(field="wavelet_model")` the section behind the outputs of a --wavelet run."""
+`reconstruct_patches(field="wavelet_model")` the section behind the outputs of a --wavelet run,
+`reconstruct_patches(field="moveout_model")` the flattened sections of a --moveout run."""
 import os
 from glob import glob
 from typing import List
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import utils as u
 
-__all__ = ["extract_patches", "load_trace_offsets", "reconstruct_patches", "patch_extractor_for", "transpose_patches_25d"]
+__all__ = ["extract_patches", "load_trace_offsets", "load_moveout", "reconstruct_patches", "patch_extractor_for", "transpose_patches_25d"]
 
 
 def patch_extractor_for(in_shape, patch_shape, patch_stride, datadim, imgchannel=None) -> u.PatchExtractor:
@@ -56,7 +57,8 @@ _transpose_patches_25d = transpose_patches_25d
 
 def extract_patches(args) -> List[dict]:
     """List of {'image': patch*gain, 'mask': binary patch, 'name': zero-padded index} (data.py:44-84).  With --trace_offsets (ours) each
-    dict gains 'offsets', the (X, Y, 2) window of the file (2-D: (X, 1, 2) with dy = 0) cut at the origin of its image and mask windows."""
+    dict gains 'offsets', the (X, Y, 2) window of the file (2-D: (X, 1, 2) with dy = 0) cut at the origin of its image and mask windows.
+    With --moveout (ours) each dict gains 'moveout': all of t and the patch's x / y window of the table."""
     original = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     corrupted = np.load(os.path.join(args.imgdir, args.maskname), allow_pickle=True)
     assert original.shape == corrupted.shape, "Original and Corrupted data must have the same dimension"
@@ -65,6 +67,7 @@ def extract_patches(args) -> List[dict]:
         corrupted = u.bool2bin(corrupted)
     off = load_trace_offsets(args, original.shape)       # --trace_offsets: refused here, before any window is cut, where it cannot be served
     pe = patch_extractor_for(original.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
+    mov = load_moveout(args, original.shape, pe)         # --moveout: refused here as well, a time-tiled patch included
     if args.datadim == "2.5d" or (args.datadim == "2d" and pe.ndim == 3):
         final_shape = (-1,) + pe.dim              # last axis = channels
     else:
@@ -80,6 +83,7 @@ def extract_patches(args) -> List[dict]:
         img = transpose_patches_25d(img, args.slice)
         msk = transpose_patches_25d(msk, args.slice)
     offs = _trace_offset_windows(args, off, original.shape, pe)
+    movs = _moveout_windows(args, mov, original.shape, pe)
     width = u.ten_digit(img.shape[0])
     out = []
     for p in range(img.shape[0]):
@@ -89,6 +93,8 @@ def extract_patches(args) -> List[dict]:
         out.append({"image": img[p] * args.gain, "mask": m, "name": str(p).zfill(width)})
         if offs is not None:
             out[-1]["offsets"] = offs[p]
+        if movs is not None:
+            out[-1]["moveout"] = movs[p]
     return out
 
 
@@ -123,6 +129,41 @@ def load_trace_offsets(args, vol_shape):
         raise ValueError("--trace_offsets %s: offsets are in grid cells and must lie in [-0.5, 0.5] (a trace belongs to the bin it is "
                          "nearest to), got |d| up to %g" % (name, float(np.abs(off).max())))
     return off
+
+
+def load_moveout(args, vol_shape, pe=None):
+    """--moveout: the table of the file as fp32 in the volume's shape — (T, X, Y) for --datadim 3d, (T, X) for --datadim 2d —, checked once
+    for the whole volume (operators.check_moveout_table); None when the flag is off.  A geometry the flag does not serve, a wrong shape,
+    non-finite values, live values that decrease along t and, with the patch extractor given, a patch that does not span the time axis
+    raise ValueError."""
+    name = getattr(args, "moveout", None)
+    if name is None:
+        return None
+    if args.datadim not in ("2d", "3d") or len(vol_shape) != (2 if args.datadim == "2d" else 3):
+        raise ValueError("--moveout needs --datadim 3d on a (T, X, Y) volume or --datadim 2d on a (T, X) section, got --datadim %s on a "
+                         "volume of shape %s" % (args.datadim, tuple(vol_shape)))
+    if pe is not None and int(pe.dim[0]) != int(vol_shape[0]):
+        raise ValueError("--moveout needs patches that span the whole time axis (%d samples), got %d along t from --patch_shape: the "
+                         "table can point anywhere along a trace, so a window in t cannot be served" % (vol_shape[0], pe.dim[0]))
+    tab = np.load(os.path.join(args.imgdir, name), allow_pickle=False)
+    if tab.shape != tuple(vol_shape) or tab.dtype.kind not in "fiu":
+        raise ValueError("--moveout %s holds %s %s for a volume of shape %s: expected real numbers of the volume's shape"
+                         % (name, tab.dtype, tuple(tab.shape), tuple(vol_shape)))
+    from .operators.moveout import check_moveout_table
+    try:
+        return check_moveout_table(tab, what="the table")[0]
+    except ValueError as e:
+        raise ValueError("--moveout %s: %s" % (name, e)) from e
+
+
+def _moveout_windows(args, tab, vol_shape, pe):
+    """The table windows (num_patches, T, X[, Y]) in the order of the image windows: all of t, the (x, y) part of the same origins."""
+    if tab is None:
+        return None
+    origins = u.window_origins(vol_shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
+    if len(vol_shape) == 2:
+        return np.stack([tab[:, int(o[1]):int(o[1]) + int(pe.dim[1])] for o in origins])
+    return np.stack([tab[:, int(o[1]):int(o[1]) + int(pe.dim[1]), int(o[2]):int(o[2]) + int(pe.dim[2])] for o in origins])
 
 
 def _trace_offset_windows(args, off, vol_shape, pe):
@@ -170,9 +211,10 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     field = "avo_model" (an --avo_theta run) re-assembles the per-patch parameter sections (T, X, 3) into (T', X', 3) with the same windows
     and weights along t and x, divided by gain (the model is linear in the data); a skipped patch counts as zeros.
     field = "wavelet_model" (a --wavelet run) re-assembles the per-patch sections behind the outputs exactly like the outputs: same windows,
-    same weights, divided by gain; a patch without one (skipped) counts as zeros."""
-    if field not in ("output", "posterior_std", "avo_model", "wavelet_model"):
-        raise ValueError("field must be output, posterior_std, avo_model or wavelet_model, got %r" % (field,))
+    same weights, divided by gain; a patch without one (skipped) counts as zeros.  field = "moveout_model" (a --moveout run) does the
+    same for the flattened sections behind the outputs."""
+    if field not in ("output", "posterior_std", "avo_model", "wavelet_model", "moveout_model"):
+        raise ValueError("field must be output, posterior_std, avo_model, wavelet_model or moveout_model, got %r" % (field,))
     if field == "avo_model":
         return _reconstruct_avo_model(args, results_root)
     cover, blend = reassembly_flags(args)
@@ -188,6 +230,8 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
         rec = np.load(path, allow_pickle=True).item()
         if field == "wavelet_model" and "wavelet" not in rec:
             raise ValueError("%s holds no wavelet_model: not the result of a --wavelet run" % path)
+        if field == "moveout_model" and "moveout" not in rec:
+            raise ValueError("%s holds no moveout_model: not the result of a --moveout run" % path)
         v = rec["output"] if field == "output" else rec.get(field)
         outs.append(np.asarray(v) if v is not None else np.zeros_like(np.asarray(rec["output"])))
         elapsed.append(rec.get("elapsed", rec.get("elapsed time")))
@@ -198,7 +242,7 @@ def reconstruct_patches(args, return_history=False, verbose=False, results_root=
     patches_out = np.asarray(outs)
     if args.datadim == "2.5d":
         patches_out = transpose_patches_25d(patches_out, args.slice, adj=True)
-    linear = field in ("output", "wavelet_model")          # blended like the data and divided by gain; else a spread
+    linear = field in ("output", "wavelet_model", "moveout_model")          # blended like the data and divided by gain; else a spread
     if not cover and blend == "flat" and linear:
         outputs = pe.reconstruct(patches_out.reshape(pa_shape)) / args.gain
     else:

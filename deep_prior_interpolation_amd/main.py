@@ -17,7 +17,8 @@ from .architectures import build_net
 from .data import extract_patches
 from .loop import LoopRule
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import check_avo, check_out_ema, check_trace_offsets_flag, check_wavelet, net_args_are_same, parse_arguments
+from .parameter import (check_avo, check_moveout, check_out_ema, check_trace_offsets_flag, check_wavelet, net_args_are_same,
+                        parse_arguments)
 
 warnings.filterwarnings("ignore")
 
@@ -54,6 +55,11 @@ class Interpolator:
         self.wavelet = check_wavelet(args)                       # None, or (file name, kind)
         self._wavelet_op = self._load_wavelet()
         self._wavelet_pre = self._wavelet_best = None            # the operator's input of this iteration / of the selected iterate
+        # --moveout (ours): the net writes the flattened gather, the moveout operator behind it reads every recorded sample from its row of
+        # the model (net_forward); muted samples leave the device mask, the section behind the selected output is kept on the device
+        self.moveout = check_moveout(args)                       # None, or (file name, interp)
+        self._moveout_op = None                                  # per patch: Moveout, table and walk ranges on the device (load_data)
+        self._moveout_pre = self._moveout_best = None            # the operator's input of this iteration / of the selected iterate
         # --trace_offsets (ours): the loss sees the grid output sampled at the recorded trace positions (data_forward)
         self.trace_offsets_file = check_trace_offsets_flag(args)
         self.trace_interp = getattr(args, "trace_interp", None) or "linear"     # --trace_interp: the kernel R samples with (linear = bilinear)
@@ -112,7 +118,48 @@ class Interpolator:
         self.mask_ = to_dev(self.mask)
         self.holdout_sel = self._holdout_dev = None
         self._load_trace_offsets(data.get("offsets"))
+        self._load_moveout(data.get("moveout"))
         return torch.std(self.img_ * self.mask_).item()
+
+    def _load_moveout(self, table):
+        """--moveout: the patch's table window -> the operator behind the network (net_forward), table and walk ranges on the device
+        before iteration 0 (a captured iteration replays it unchanged).  The DEVICE mask is multiplied by the live map, so a muted sample
+        counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped); the host mask that is saved
+        stays the file's."""
+        self._moveout_op = None
+        if self.moveout is None:
+            if table is not None:
+                raise ValueError("patch %s carries a moveout table but --moveout is off" % (self.image_name,))
+            return
+        if table is None:
+            raise ValueError("--moveout %s: patch %s carries no table (data.extract_patches cuts it)" % (self.moveout[0], self.image_name))
+        table = np.asarray(table)
+        if table.shape != tuple(self.img.shape[:-1]):
+            raise ValueError("--moveout: a table of shape %s does not belong to a patch of shape %s: expected %s (all of t, the patch's "
+                             "traces)" % (tuple(table.shape), tuple(self.img.shape), tuple(self.img.shape[:-1])))
+        from .operators import Moveout
+        try:
+            op = Moveout(table, interp=self.moveout[1])
+        except ValueError as e:
+            raise ValueError("--moveout: %s" % e) from e
+        if self.device.type == "cuda":
+            op.upload(self.device)
+        self._moveout_op = op
+        self.mask_ = self.mask_ * torch.from_numpy(op.live.astype(np.float32)).to(self.device)[None, None]
+
+    def known_mask(self):
+        """The host mask of the samples that count: the file's, with --moveout without the muted samples."""
+        if self._moveout_op is None:
+            return self.mask
+        return self.mask * self._moveout_op.live[..., None].astype(self.mask.dtype)
+
+    def moveout_model(self):
+        """--moveout: the flattened section behind the selected output — the operator's input at the selected iteration — in the numpy
+        order and shape of `output`, in the patch's gained units.  None for a patch that was not optimised, and with --out_ema or a
+        sampler: the selected output there is an average of iterates whose model is not tracked."""
+        if self._moveout_op is None or self._moveout_best is None or self.out_ema > 0.0 or self.is_sampler():
+            return None
+        return self._to_numpy_out(self._moveout_best)
 
     def _load_wavelet(self):
         """--wavelet: the file in --imgdir -> the operator, its taps on the device before iteration 0 (a captured iteration replays it
@@ -177,7 +224,7 @@ class Interpolator:
         the (C, S...) float 0/1 tensor the loss pass reads, in self._holdout_dev."""
         if self.holdout <= 0.0:
             return
-        self.holdout_sel = u.holdout_traces(self.mask, self.holdout, self.noise_seed, name=self.image_name)
+        self.holdout_sel = u.holdout_traces(self.known_mask(), self.holdout, self.noise_seed, name=self.image_name)
         dev = np.moveaxis(self.holdout_sel, -1, 0)                # (C, X[, Y]): the trace index (c, s) of the device layout (1, C, T, S...)
         self._holdout_dev = torch.from_numpy(np.ascontiguousarray(dev)).to(self.device)
 
@@ -314,14 +361,17 @@ class Interpolator:
         main.py:159, which its PartialUNet.forward(x, mask) cannot serve): training_mask(), so held-out traces are holes for the net too, as one
         channel (amax over dim 1: the 2.5-D slab's channels; in 3-D the mask itself).  Constant per patch: built once, so a captured
         iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
-        them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m): what this returns is a data-domain
-        tensor either way."""
+        them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m); with --moveout the network writes
+        the flattened gather and the moveout operator comes last (d = L m): what this returns is a data-domain tensor either way."""
         out = self._net_forward(z)
         if self.avo is not None:
             out = self._avo_operator(int(z.shape[2]))(out)
         if self._wavelet_op is not None:
             self._wavelet_pre = out.detach()                     # kept when this iterate is selected (wavelet_model)
             out = self._wavelet_op(out)
+        if self._moveout_op is not None:
+            self._moveout_pre = out.detach()                     # kept when this iterate is selected (moveout_model)
+            out = self._moveout_op(out)
         return out
 
     def _avo_operator(self, nt0):
@@ -577,6 +627,8 @@ class Interpolator:
             self._out_best_dev = out_.detach()       # stays on the GPU; copied to the host once, after the loop
             if self._wavelet_op is not None:
                 self._wavelet_best = self._wavelet_pre                   # W is not invertible: the section behind it is kept beside it
+            if self._moveout_op is not None:
+                self._moveout_best = self._moveout_pre                   # nor is L: the flattened section is kept beside the output
         if self.iiter in self.iter_to_be_saved and self.iiter != 0:
             np.save(os.path.join(self.outpath, self.image_name.split(".")[0]
                                  + "_output%s.npy" % str(self.iiter).zfill(self.zfill)), self._to_numpy_out(out_))
@@ -762,9 +814,10 @@ class Interpolator:
             best_src = self._ema_avg if rule.ema else out_       # --out_ema: the selected AVERAGE is kept
             _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(best_src), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
-            if self._wavelet_op is not None and not rule.ema:
-                # --wavelet: the section behind the selected iterate, on the same flag, into a buffer of its own
-                pre = self._wavelet_pre
+            pre_op = self._wavelet_op if self._wavelet_op is not None else self._moveout_op       # the two flags exclude each other
+            if pre_op is not None and not rule.ema:
+                # --wavelet / --moveout: the section behind the selected iterate, on the same flag, into a buffer of its own
+                pre = self._wavelet_pre if self._wavelet_op is not None else self._moveout_pre
                 if self._g_wbest is None:
                     self._g_wbest = torch.empty_like(pre)
                 _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(pre), _lib.ptr(self._g_wbest), pre.numel(),
@@ -801,7 +854,8 @@ class Interpolator:
         self._g_rule.fill(self, self.history, h, st)
         self.iiter = n
         self._out_best_dev = self._g_best
-        self._wavelet_best = self._g_wbest
+        self._wavelet_best = self._g_wbest if self._wavelet_op is not None else None
+        self._moveout_best = self._g_wbest if self._moveout_op is not None else None
         self.out_best = self._to_numpy_out(self._g_best)
         self._finish_posterior()
 
@@ -855,6 +909,10 @@ class Interpolator:
         if self._wavelet_op is not None:
             # the taps as used (w, or w / 2 for impedance) and the section behind `output`; None: see wavelet_model()
             run.update(wavelet=self._wavelet_op.taps.copy(), wavelet_model_kind=self._wavelet_op.kind, wavelet_model=self.wavelet_model())
+        if self.moveout is not None:
+            # the fp32 table window as used and the flattened section behind `output`; None: see moveout_model()
+            run.update(moveout=None if self._moveout_op is None else self._moveout_op.table.copy(), moveout_interp=self.moveout[1],
+                       moveout_model=self.moveout_model())
         if self.trace_offsets_file is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
             run["trace_interp"] = self.trace_interp
@@ -871,6 +929,7 @@ class Interpolator:
         self.best_iter = self.val_min = self.ema_min = None
         self._out_best_dev = None
         self._wavelet_pre = self._wavelet_best = None            # the section behind the output belongs to the patch
+        self._moveout_pre = self._moveout_best = None
         self._ema_avg = self._ema_best = None                    # the running average belongs to the patch
         self._reset_posterior()
         self._zero_moments()

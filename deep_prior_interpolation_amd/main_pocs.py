@@ -43,6 +43,9 @@ class Interpolator(_Base):
         if getattr(args, "wavelet", None) is not None:
             raise ValueError("main_pocs does not support --wavelet: the POCS projection re-inserts the known traces into the output, which "
                              "takes it out of the range of the wavelet operator; run main.py")
+        if getattr(args, "moveout", None) is not None:
+            raise ValueError("main_pocs does not support --moveout: the POCS projection thresholds and re-inserts traces in the data "
+                             "domain, the network writes the flattened one; run main.py")
         super().__init__(args, outpath, device=device, seed=seed)
         self.history = u.HistoryReg(args.epochs)
         self.pocs = None

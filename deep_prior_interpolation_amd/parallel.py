@@ -559,7 +559,7 @@ def main(argv=None):
         u.write_args(os.path.join(outpath, "args.txt"), args)
     if world > 1:
         dist.barrier()
-    patches = extract_patches(args)          # with --trace_offsets each dict carries its "offsets" window to load_data; re-assembly blends grid outputs
+    patches = extract_patches(args)          # with --trace_offsets / --moveout each dict carries its "offsets" / "moveout" window to load_data
     vol = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     pe = patch_extractor_for(vol.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
     origins = u.window_origins(vol.shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
@@ -612,9 +612,19 @@ def main(argv=None):
         if rank == 0:
             from .data import reconstruct_patches
             volumes["model"] = reconstruct_patches(args, field="wavelet_model")
+    if getattr(args, "moveout", None) is not None and not sampler and not (getattr(args, "out_ema", 0.0) or 0.0):
+        # --moveout: the flattened sections behind reconstructed.npy, re-assembled the same way (every patch spans the time axis, so the
+        # windows overlap in x / y only, where the model lives on the data's grid)
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            from .data import reconstruct_patches
+            volumes["flat"] = reconstruct_patches(args, field="moveout_model")
     _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
+        if volumes.get("flat") is not None:
+            np.save(os.path.join(outpath, "reconstructed_flat.npy"), volumes["flat"])
         if volumes.get("model") is not None:
             np.save(os.path.join(outpath, "reconstructed_model.npy"), volumes["model"])
         if sampler and volumes.get("std") is not None:

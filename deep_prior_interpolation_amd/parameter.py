@@ -149,6 +149,17 @@ _FLAGS = [
     (("--wavelet_model",), dict(type=str, required=False, default="reflectivity", choices=["reflectivity", "impedance"],
                                help="ours: what the network writes under --wavelet: reflectivity = r, traces d = w * r; impedance = m = ln(AI), "
                                     "traces d = 0.5 w * D m with D the forward difference along t; needs --wavelet")),
+    # moveout along t (ours: the reference warps no axis)
+    (("--moveout",), dict(type=str, required=False,
+                         help="ours: a .npy in --imgdir with a moveout table tau (absent = off): (T, X, Y) for --datadim 3d on a (T, X, Y) "
+                              "volume, (T, X) for --datadim 2d on a (T, X) section.  The network then writes the flattened gather m and "
+                              "the loss sees d[t] = m[tau[t]] of the same trace (NMO, LMO, flattening on a horizon: operators.nmo_table, "
+                              "shift_table); a sample is live where 0 <= tau <= T - 1, any other finite value (-1) mutes it: d = 0 there "
+                              "and it counts in no loss.  The live values of a trace must not decrease along t and a patch must span the "
+                              "whole time axis; the section is saved as moveout_model")),
+    (("--moveout_interp",), dict(type=str, required=False, default="linear", choices=["linear", "cubic"],
+                                help="ours: how --moveout reads the model along t: linear = 2 taps, cubic = 4 taps (Keys, a = -1/2); needs "
+                                     "--moveout")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -189,6 +200,7 @@ def postprocess(args: Namespace) -> Namespace:
     check_trace_offsets_flag(args)
     check_avo(args)
     check_wavelet(args)
+    check_moveout(args)
     return args
 
 
@@ -236,6 +248,34 @@ def check_wavelet(args: Namespace):
         raise ValueError("--wavelet needs the time axis as dim 2 of the patch: --datadim 2d, 3d, or 2.5d with --slice tx or ty; "
                          "--slice %s stacks t into the channels" % args.slice)
     return name, kind
+
+
+def check_moveout(args: Namespace):
+    """--moveout and what it cannot be combined with; returns None when it is off (also for a Namespace without the keys, as those of
+    older args.txt files), else (file name, interp).  The file itself is read and checked by data.extract_patches, which also refuses a
+    patch that does not span the time axis."""
+    name = getattr(args, "moveout", None)
+    interp = getattr(args, "moveout_interp", None) or "linear"
+    if interp not in ("linear", "cubic"):
+        raise ValueError("--moveout_interp must be linear or cubic, got %r" % (interp,))
+    if name is None:
+        if interp != "linear":
+            raise ValueError("--moveout_interp %s needs --moveout: without a table nothing is moved and the flag would silently do "
+                             "nothing" % interp)
+        return None
+    if args.datadim not in ("2d", "3d"):
+        raise ValueError("--moveout needs --datadim 2d or 3d, got --datadim %s: a 2.5-D slab is not served" % args.datadim)
+    if getattr(args, "avo_theta", None) is not None:
+        raise ValueError("--moveout does not combine with --avo_theta, which needs --datadim 2.5d")
+    if getattr(args, "wavelet", None) is not None:
+        raise ValueError("--moveout does not combine with --wavelet: which of the two operators comes first is not decided yet")
+    if getattr(args, "net", "multiunet") == "part":
+        raise ValueError("--moveout does not combine with --net part: its hole map would live on the model's time axis, the mask on the "
+                         "data's")
+    if (getattr(args, "data_forgetting_factor", 0) or 0) > 0:
+        raise ValueError("--moveout does not combine with --data_forgetting_factor %d: it adds data-domain traces to the input of a "
+                         "network that writes the model domain" % args.data_forgetting_factor)
+    return name, interp
 
 
 def check_avo(args: Namespace):
@@ -336,6 +376,11 @@ def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
         errors.append("wavelet")
     if (a.get("wavelet_model") or "reflectivity") != (b.get("wavelet_model") or "reflectivity"):
         errors.append("wavelet_model")
+    # --moveout / --moveout_interp (ours) decide what the network's output means; an args.txt without the keys: off / linear
+    if a.get("moveout") != b.get("moveout"):
+        errors.append("moveout")
+    if (a.get("moveout_interp") or "linear") != (b.get("moveout_interp") or "linear"):
+        errors.append("moveout_interp")
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

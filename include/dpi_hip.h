@@ -639,6 +639,26 @@ int dpi_avo_adj(const float* y, const float* G, int ntheta, int T, size_t S, flo
 int dpi_wavelet_fwd(const float* m, const float* taps, int K, int diff, int C, int T, size_t S, float* d, void* stream);
 int dpi_wavelet_adj(const float* d, const float* taps, int K, int diff, int C, int T, size_t S, float* m, void* stream);
 
+/* ---------------------------------------------------------------- Moveout along t (--moveout) --
+ * Ours (the reference warps no axis): d = L m reads every recorded sample from a fractional row of its own trace column of the model m,
+ * the flattened gather the network writes.  Tensors [C][T][S] fp32, contiguous, S = X or X * Y: one layout for (1, C, T, X) and
+ * (1, C, T, X, Y).  tau: [T][S] fp32 on the device, shared by the channels; a sample is live when 0 <= tau <= T - 1 and muted otherwise.
+ *     interp 0, linear: i0 = floor(tau), f = tau - i0, rows i0, i0 + 1 with the weights 1 - f, f.
+ *     interp 1, cubic:  Keys, a = -1/2, rows i0 - 1 .. i0 + 2 with ((-.5f+1)f-.5)f, (1.5f-2.5)f^2+1, ((-1.5f+2)f+.5)f, (.5f-.5)f^2.
+ * Row indices clamp to [0, T - 1] and every clamped tap counts.
+ *     dpi_moveout_fwd:  d[c][t][s] = sum_k w_k(tau[t][s]) * m[c][row_k][s] in ascending k from the first product; 0 where muted.
+ *     dpi_moveout_adj:  the exact transpose as a gather without atomics: m[c][i][s] = the sum, in ascending t then k, of w_k d[c][t][s]
+ *                       over the live samples range[0][i][s] <= t < range[1][i][s] of column s whose tap k lands on row i (rows 0 and
+ *                       T - 1 collect the clamped taps).  range: [2][T][S] int32 on the device; any range that holds every live sample
+ *                       touching row i gives the same bits (for a table whose live values do not decrease along t those samples are
+ *                       contiguous among the live ones: operators/moveout.py builds the tightest range).  The bounds are clamped to
+ *                       [0, T] and every tap is checked against i: no table or range reads or writes out of bounds.
+ * The weights come from the same fp32 expressions both ways; f = 0 gives 1, 0 / 0, 1, 0, 0 exactly, so the identity table is the identity
+ * bit for bit.  Null or aliased pointers, interp other than 0 / 1, C, T, S < 1 and T > 2^24 return an error before any launch.  ABI version
+ * stays: a stale library fails on the unresolved symbols. */
+int dpi_moveout_fwd(const float* m, const float* tau, int interp, int C, int T, size_t S, float* d, void* stream);
+int dpi_moveout_adj(const float* d, const float* tau, const int* range, int interp, int C, int T, size_t S, float* m, void* stream);
+
 /* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
  * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
  * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]
