@@ -15,10 +15,10 @@ from . import _lib, ops
 from . import utils as u
 from .architectures import build_net
 from .data import extract_patches
+from .forward_model import ForwardModel, to_numpy_out
 from .loop import LoopRule
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import (check_avo, check_moveout, check_out_ema, check_trace_offsets_flag, check_wavelet, net_args_are_same,
-                        parse_arguments)
+from .parameter import check_out_ema, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -47,24 +47,9 @@ class Interpolator:
         self.out_ema = check_out_ema(args)
         self._ema_avg = self._ema_best = self._ema_one = None    # per patch: the average, its selected snapshot, a constant 1 flag
         self.ema_min = None
-        # --avo_theta (ours): the net outputs three elastic-parameter sections, the AVO operator maps them to the angle sections (net_forward)
-        self.avo = check_avo(args)                               # None, or (theta, vsvp, linearization)
-        self._avo_op = None                                      # built per patch length T (net_forward)
-        # --wavelet (ours): the net writes a reflectivity / log-impedance section, the wavelet operator behind it (and behind the AVO
-        # operator) maps it to the traces (net_forward); the section behind the selected output is kept on the device
-        self.wavelet = check_wavelet(args)                       # None, or (file name, kind)
-        self._wavelet_op = self._load_wavelet()
-        self._wavelet_pre = self._wavelet_best = None            # the operator's input of this iteration / of the selected iterate
-        # --moveout (ours): the net writes the flattened gather, the moveout operator behind it reads every recorded sample from its row of
-        # the model (net_forward); muted samples leave the device mask, the section behind the selected output is kept on the device
-        self.moveout = check_moveout(args)                       # None, or (file name, interp)
-        self._moveout_op = None                                  # per patch: Moveout, table and walk ranges on the device (load_data)
-        self._moveout_pre = self._moveout_best = None            # the operator's input of this iteration / of the selected iterate
-        # --trace_offsets (ours): the loss sees the grid output sampled at the recorded trace positions (data_forward)
-        self.trace_offsets_file = check_trace_offsets_flag(args)
-        self.trace_interp = getattr(args, "trace_interp", None) or "linear"     # --trace_interp: the kernel R samples with (linear = bilinear)
-        self.trace_offsets = None                                # per patch: (X, Y, 2) as used, i.e. zero at unknown traces
-        self._sampling_op = None                                 # per patch: TraceSampling, its offsets on the device (load_data)
+        # --avo_theta, --wavelet, --moveout, --trace_offsets (ours): the operators between the network and the loss (net_forward,
+        # data_forward) and what is kept of them for the selected output
+        self.forward_model = ForwardModel(args)
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
         self.optimizer_kind = getattr(args, "optimizer", "adam")
         if self.optimizer_kind not in ("adam", "sgld", "psgld"):
@@ -117,106 +102,41 @@ class Interpolator:
         self.img_ = to_dev(self.img)
         self.mask_ = to_dev(self.mask)
         self.holdout_sel = self._holdout_dev = None
-        self._load_trace_offsets(data.get("offsets"))
-        self._load_moveout(data.get("moveout"))
+        live = self.forward_model.load_patch(data, self.img.shape, self.mask, self.device, self.image_name)
+        if live is not None:                                     # --moveout: muted samples count nowhere; the host mask that is saved stays the file's
+            self.mask_ = self.mask_ * torch.from_numpy(live.astype(np.float32)).to(self.device)[None, None]
         return torch.std(self.img_ * self.mask_).item()
-
-    def _load_moveout(self, table):
-        """--moveout: the patch's table window -> the operator behind the network (net_forward), table and walk ranges on the device
-        before iteration 0 (a captured iteration replays it unchanged).  The DEVICE mask is multiplied by the live map, so a muted sample
-        counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped); the host mask that is saved
-        stays the file's."""
-        self._moveout_op = None
-        if self.moveout is None:
-            if table is not None:
-                raise ValueError("patch %s carries a moveout table but --moveout is off" % (self.image_name,))
-            return
-        if table is None:
-            raise ValueError("--moveout %s: patch %s carries no table (data.extract_patches cuts it)" % (self.moveout[0], self.image_name))
-        table = np.asarray(table)
-        if table.shape != tuple(self.img.shape[:-1]):
-            raise ValueError("--moveout: a table of shape %s does not belong to a patch of shape %s: expected %s (all of t, the patch's "
-                             "traces)" % (tuple(table.shape), tuple(self.img.shape), tuple(self.img.shape[:-1])))
-        from .operators import Moveout
-        try:
-            op = Moveout(table, interp=self.moveout[1])
-        except ValueError as e:
-            raise ValueError("--moveout: %s" % e) from e
-        if self.device.type == "cuda":
-            op.upload(self.device)
-        self._moveout_op = op
-        self.mask_ = self.mask_ * torch.from_numpy(op.live.astype(np.float32)).to(self.device)[None, None]
 
     def known_mask(self):
         """The host mask of the samples that count: the file's, with --moveout without the muted samples."""
-        if self._moveout_op is None:
-            return self.mask
-        return self.mask * self._moveout_op.live[..., None].astype(self.mask.dtype)
+        live = self.forward_model.live
+        return self.mask if live is None else self.mask * live[..., None].astype(self.mask.dtype)
 
     def moveout_model(self):
-        """--moveout: the flattened section behind the selected output — the operator's input at the selected iteration — in the numpy
-        order and shape of `output`, in the patch's gained units.  None for a patch that was not optimised, and with --out_ema or a
-        sampler: the selected output there is an average of iterates whose model is not tracked."""
-        if self._moveout_op is None or self._moveout_best is None or self.out_ema > 0.0 or self.is_sampler():
-            return None
-        return self._to_numpy_out(self._moveout_best)
-
-    def _load_wavelet(self):
-        """--wavelet: the file in --imgdir -> the operator, its taps on the device before iteration 0 (a captured iteration replays it
-        unchanged).  None when the flag is off."""
-        if self.wavelet is None:
-            return None
-        name, kind = self.wavelet
-        from .operators import ConvolutionalModelling
-        path = os.path.join(self.args.imgdir, name)
-        try:
-            op = ConvolutionalModelling(np.load(path, allow_pickle=False), kind=kind)
-        except (OSError, ValueError) as e:
-            raise ValueError("--wavelet %s: %s" % (path, e)) from e
-        if self.device.type == "cuda":
-            op.upload(self.device)
-        return op
+        """--moveout: the flattened section behind the selected output (ForwardModel.model)."""
+        return self.forward_model.model("moveout")
 
     def wavelet_model(self):
-        """--wavelet: the section behind the selected output — the operator's input at the selected iteration, i.e. the reflectivity or
-        log-impedance section (behind --avo_theta: the angle sections before the wavelet) — in the numpy order and shape of `output`, in
-        the patch's gained units.  None for a patch that was not optimised, and with --out_ema or a sampler: the selected output there is
-        an average of iterates whose model is not tracked."""
-        if self._wavelet_op is None or self._wavelet_best is None or self.out_ema > 0.0 or self.is_sampler():
-            return None
-        return self._to_numpy_out(self._wavelet_best)
+        """--wavelet: the reflectivity or log-impedance section behind the selected output — behind --avo_theta: the angle sections
+        before the wavelet (ForwardModel.model)."""
+        return self.forward_model.model("wavelet")
 
-    def _load_trace_offsets(self, offsets):
-        """--trace_offsets: the patch's (X, Y, 2) offsets -> the sampling operator behind the network's output (data_forward).  Offsets of
-        traces the mask marks unknown are zeroed: the operator is the identity there, so nothing off-grid leaks into a trace no data
-        belongs to.  The offsets go to the device here, before iteration 0: a captured iteration replays the operator unchanged."""
-        self.trace_offsets = self._sampling_op = None
-        if self.trace_offsets_file is None:
-            if offsets is not None:
-                raise ValueError("patch %s carries trace offsets but --trace_offsets is off" % (self.image_name,))
-            return
-        if offsets is None:
-            raise ValueError("--trace_offsets %s: patch %s carries no offsets (data.extract_patches cuts them)"
-                             % (self.trace_offsets_file, self.image_name))
-        off = np.asarray(offsets, dtype=np.float32)
-        if self.img.ndim not in (3, 4) or off.shape != (self.img.shape[1], self.img.shape[2] if self.img.ndim == 4 else 1, 2):
-            raise ValueError("--trace_offsets: offsets %s do not belong to a patch of shape %s: expected (X, Y, 2)"
-                             % (tuple(off.shape), tuple(self.img.shape)))
-        known = (np.asarray(self.mask) != 0).any(axis=(0, -1)).reshape(off.shape[:2])
-        self.trace_offsets = off * known[..., None].astype(np.float32)
-        from .operators import TraceSampling
-        try:
-            self._sampling_op = TraceSampling(np.moveaxis(self.trace_offsets, -1, 0), interp=self.trace_interp)       # [2][X][Y]
-        except ValueError as e:
-            raise ValueError("--trace_offsets: %s" % e) from e
-        self._sampling_op.upload(self.device)
+    def avo_model(self):
+        """--avo_theta: the three parameter sections (T, X, 3) behind the selected output (ForwardModel.model).  Every selected output —
+        the best iterate, the running average, the posterior mean — is a linear combination of iterates G m_i, so the pseudo-inverse
+        returns the same combination of the m_i: no second tracking path on the device.  None for a patch that was not optimised."""
+        return self.forward_model.model("avo", self._optimised_output())
+
+    def _optimised_output(self):
+        return None if self._out_best_dev is None else self.out_best
+
+    trace_offsets = property(lambda self: self.forward_model.trace_offsets, doc="per patch: (X, Y, 2) as used, i.e. zero at unknown traces")
+    trace_interp = property(lambda self: self.forward_model.trace_interp, doc="--trace_interp: the kernel R samples with")
 
     def data_forward(self, out_):
         """What the loss compares with the recorded traces: the grid output itself, or with --trace_offsets the grid output sampled at the
         recorded trace positions.  Everything that keeps an output (out_best, --save_every, the --aa_weight term) keeps the grid tensor."""
-        if self._sampling_op is None:
-            return out_
-        return self._sampling_op(out_)                           # fp32 in every --precision mode: the output layer writes fp32
+        return self.forward_model.apply_data(out_)
 
     def build_holdout(self):
         """--holdout: draw the per-trace split of the loaded patch from the patch seed (begin_patch) and upload it once.  optimize() and
@@ -363,36 +283,7 @@ class Interpolator:
         iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
         them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m); with --moveout the network writes
         the flattened gather and the moveout operator comes last (d = L m): what this returns is a data-domain tensor either way."""
-        out = self._net_forward(z)
-        if self.avo is not None:
-            out = self._avo_operator(int(z.shape[2]))(out)
-        if self._wavelet_op is not None:
-            self._wavelet_pre = out.detach()                     # kept when this iterate is selected (wavelet_model)
-            out = self._wavelet_op(out)
-        if self._moveout_op is not None:
-            self._moveout_pre = out.detach()                     # kept when this iterate is selected (moveout_model)
-            out = self._moveout_op(out)
-        return out
-
-    def _avo_operator(self, nt0):
-        """--avo_theta: the operator of the loaded patch (nt0 = its T), built once and kept while T stays the same; its coefficients are
-        uploaded at its first call, i.e. in the eager iteration 0 of a captured run."""
-        if self._avo_op is None or self._avo_op.nt0 != nt0:
-            from .operators import AVOLinearModelling
-            theta, vsvp, lin = self.avo
-            self._avo_op = AVOLinearModelling(theta, vsvp=vsvp, nt0=nt0, spatdims=(1,), linearization=lin)
-        return self._avo_op
-
-    def avo_model(self):
-        """--avo_theta: the three parameter sections (T, X, 3) behind the selected output, m_t = pinv(G_t) out_best_t per time sample in
-        float64 with the fp32 G of the device, stored as fp32.  Every selected output — the best iterate, the running average, the posterior
-        mean — is a linear combination of iterates G m_i, so this returns the same combination of the m_i: no second tracking path on the
-        device.  None for a patch that was not optimised."""
-        if self.avo is None or self._out_best_dev is None or self.out_best is None:
-            return None
-        from .operators import avo_model_from_data
-        op = self._avo_operator(int(self.out_best.shape[0]))
-        return avo_model_from_data(self.out_best, op.G.numpy().reshape(op.ntheta, 3, op.nt0)).astype(np.float32)
+        return self.forward_model.apply_model(self._net_forward(z))
 
     def _net_forward(self, z):
         if getattr(self.args, "net", "multiunet") != "part":
@@ -420,7 +311,7 @@ class Interpolator:
 
     def net_outchannel(self):
         """Channels the network itself writes: the patch's, or with --avo_theta the three parameter sections."""
-        return 3 if self.avo is not None else self.outchannel
+        return self.forward_model.net_outchannel(self.outchannel)
 
     def build_model(self, netpath=None):
         self.release_packed_weights()
@@ -525,9 +416,7 @@ class Interpolator:
         inp = inp.to(self.device)
         return inp.to(torch.bfloat16) if (ops.storage_bf16() and inp.ndim == 5) else inp
 
-    def _to_numpy_out(self, out_):
-        """(1,1,T,X,Y) -> (T,X,Y) ; (1,C,H,W) -> (H,W,C)  (main.py:175-176)."""
-        return u.torch_to_np(out_, True) if out_.ndim > 4 else u.torch_to_np(out_, False)[0].transpose((1, 2, 0))
+    _to_numpy_out = staticmethod(to_numpy_out)
 
     def precision_scope(self):
         """--precision of THIS Interpolator as an ops.mode_scope: the arithmetic mode of the convolutions and the storage type of the activations of
@@ -625,10 +514,7 @@ class Interpolator:
             self._out_best_dev = self._ema_best
         elif improved:
             self._out_best_dev = out_.detach()       # stays on the GPU; copied to the host once, after the loop
-            if self._wavelet_op is not None:
-                self._wavelet_best = self._wavelet_pre                   # W is not invertible: the section behind it is kept beside it
-            if self._moveout_op is not None:
-                self._moveout_best = self._moveout_pre                   # nor is L: the flattened section is kept beside the output
+            self.forward_model.select()              # W and L are not invertible: the section behind the output is kept beside it
         if self.iiter in self.iter_to_be_saved and self.iiter != 0:
             np.save(os.path.join(self.outpath, self.image_name.split(".")[0]
                                  + "_output%s.npy" % str(self.iiter).zfill(self.zfill)), self._to_numpy_out(out_))
@@ -793,7 +679,8 @@ class Interpolator:
         self._ensure_holdout()
         rule = self._g_rule = self.loop_rule()
         self._g_state, self._g_hist, self._g_improved = rule.new_state(a.epochs, dev)
-        self._g_best = self._g_wbest = None
+        self._g_best = None
+        self.forward_model.new_buffer()
 
         def one_iteration():
             with self.precision_scope():
@@ -814,14 +701,8 @@ class Interpolator:
             best_src = self._ema_avg if rule.ema else out_       # --out_ema: the selected AVERAGE is kept
             _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(best_src), _lib.ptr(self._g_best), out_.numel(),
                                      _lib.stream()), "dpi_copy_if")
-            pre_op = self._wavelet_op if self._wavelet_op is not None else self._moveout_op       # the two flags exclude each other
-            if pre_op is not None and not rule.ema:
-                # --wavelet / --moveout: the section behind the selected iterate, on the same flag, into a buffer of its own
-                pre = self._wavelet_pre if self._wavelet_op is not None else self._moveout_pre
-                if self._g_wbest is None:
-                    self._g_wbest = torch.empty_like(pre)
-                _lib.check(L.dpi_copy_if(_lib.ptr(self._g_improved), _lib.ptr(pre), _lib.ptr(self._g_wbest), pre.numel(),
-                                         _lib.stream()), "dpi_copy_if")
+            if not rule.ema:
+                self.forward_model.select_if(self._g_improved)       # the section behind the selected iterate, on the same flag
 
         one_iteration()                                  # iteration 0, eager (also warms every lazy cache)
         if quiet_device:
@@ -854,8 +735,7 @@ class Interpolator:
         self._g_rule.fill(self, self.history, h, st)
         self.iiter = n
         self._out_best_dev = self._g_best
-        self._wavelet_best = self._g_wbest if self._wavelet_op is not None else None
-        self._moveout_best = self._g_wbest if self._moveout_op is not None else None
+        self.forward_model.take_buffer()
         self.out_best = self._to_numpy_out(self._g_best)
         self._finish_posterior()
 
@@ -904,18 +784,7 @@ class Interpolator:
         if self.out_ema > 0.0:
             run["out_ema"] = self.out_ema                        # `output` is the selected running average, best_iter its iteration
             run["best_iter"] = self.best_iter
-        if self.avo is not None:
-            run.update(avo_theta=list(self.avo[0]), avo_vsvp=self.avo[1], avo_linearization=self.avo[2], avo_model=self.avo_model())
-        if self._wavelet_op is not None:
-            # the taps as used (w, or w / 2 for impedance) and the section behind `output`; None: see wavelet_model()
-            run.update(wavelet=self._wavelet_op.taps.copy(), wavelet_model_kind=self._wavelet_op.kind, wavelet_model=self.wavelet_model())
-        if self.moveout is not None:
-            # the fp32 table window as used and the flattened section behind `output`; None: see moveout_model()
-            run.update(moveout=None if self._moveout_op is None else self._moveout_op.table.copy(), moveout_interp=self.moveout[1],
-                       moveout_model=self.moveout_model())
-        if self.trace_offsets_file is not None:
-            run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
-            run["trace_interp"] = self.trace_interp
+        run.update(self.forward_model.run_fields(self._optimised_output()))
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)
@@ -928,8 +797,7 @@ class Interpolator:
         self.loss_min = None
         self.best_iter = self.val_min = self.ema_min = None
         self._out_best_dev = None
-        self._wavelet_pre = self._wavelet_best = None            # the section behind the output belongs to the patch
-        self._moveout_pre = self._moveout_best = None
+        self.forward_model.clean()
         self._ema_avg = self._ema_best = None                    # the running average belongs to the patch
         self._reset_posterior()
         self._zero_moments()

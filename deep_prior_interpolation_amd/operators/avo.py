@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import LinearOpFn
+from .base import LinearOperator
 
 __all__ = ["AVOLinearModelling", "avo_coefficients", "avo_model_from_data", "AVO_LINEARIZATIONS"]
 
@@ -59,7 +59,7 @@ def avo_model_from_data(data, G):
     return np.einsum("tka,tsa->tsk", P, flat).reshape(d.shape[:-1] + (3,))
 
 
-class AVOLinearModelling(torch.nn.Module):
+class AVOLinearModelling(LinearOperator):
     """forward: (1, 3, nt0, *spat) -> (1, ntheta, nt0, *spat); adjoint: back (avo.py:43-95).  `G` keeps the reference's shape
     (ntheta, 3, nt0, 1[, 1]) (fp32, on the host; also for nt0 = 1, where the reference drops the time axis).  Differences, all refusals of what
     the reference computes garbage for or fails on later: an unknown linearization and |theta| >= 90 raise ValueError; a batch other than 1,
@@ -78,14 +78,14 @@ class AVOLinearModelling(torch.nn.Module):
         self.G64 = avo_coefficients(theta, vsvp, self.nt0, linearization)          # (ntheta, 3, nt0) float64
         self._g32 = np.ascontiguousarray(self.G64.astype(np.float32))              # the one rounding
         self.G = torch.from_numpy(self._g32.reshape(self._g32.shape + (1,) * len(self.spatdims)))
-        self._dev = {}
+        self._ndim_msg = "AVOLinearModelling built for %d spatial axes got a %%d-D tensor" % len(self.spatdims)
 
-    def _apply(self, x, adjoint):
+    def _to_device(self, device):
+        return torch.from_numpy(self._g32).to(device)
+
+    def _matvec(self, x, adjoint):
         cin = self.ntheta if adjoint else 3
-        if x.ndim != 3 + len(self.spatdims):
-            raise _lib.DpiError("AVOLinearModelling built for %d spatial axes got a %d-D tensor" % (len(self.spatdims), x.ndim))
-        if x.shape[0] != 1:
-            raise _lib.DpiError("AVOLinearModelling works on one patch at a time: batch size %d" % x.shape[0])
+        self._check_patch(x, _lib.DpiError, self._ndim_msg, ndims=(3 + len(self.spatdims),))
         if x.shape[1] != cin:
             raise _lib.DpiError("AVOLinearModelling.%s expects %d channels, got %d" % ("adjoint" if adjoint else "forward", cin, x.shape[1]))
         if x.shape[2] != self.nt0:
@@ -95,18 +95,9 @@ class AVOLinearModelling(torch.nn.Module):
             S *= int(n)
         if S < 1:
             raise _lib.DpiError("AVOLinearModelling: empty tensor %s" % (tuple(x.shape),))
-        g = self._dev.get(str(x.device))
-        if g is None:
-            g = torch.from_numpy(self._g32).to(x.device)
-            self._dev[str(x.device)] = g
+        g = self.upload(x.device)
         y = torch.empty((1, 3 if adjoint else self.ntheta) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
         L = _lib.load()
         fn, name = (L.dpi_avo_adj, "dpi_avo_adj") if adjoint else (L.dpi_avo_fwd, "dpi_avo_fwd")
         _lib.check(fn(_lib.ptr(x), _lib.ptr(g), self.ntheta, self.nt0, S, _lib.ptr(y), _lib.stream()), name)
         return y
-
-    def forward(self, x):
-        return LinearOpFn.apply(x, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)

@@ -3,22 +3,58 @@ import torch
 
 from .. import _lib
 
-__all__ = ["Chain", "dottest", "Hessian", "LinearOpFn"]
+__all__ = ["Chain", "dottest", "Hessian", "LinearOpFn", "LinearOperator"]
 
 
 class LinearOpFn(torch.autograd.Function):
-    """y = A x for a linear operator object with `_apply(x, adjoint)`; backward = A^T dy (and A dy for the adjoint call)."""
+    """y = A x for a linear operator object with `_matvec(x, adjoint)`; backward = A^T dy (and A dy for the adjoint call)."""
 
     @staticmethod
     def forward(ctx, x, op, adjoint):
         if not x.is_cuda or x.dtype != torch.float32:
             raise _lib.DpiError("operators run on fp32 GPU tensors (no CPU path)")
         ctx.op, ctx.adjoint = op, bool(adjoint)
-        return op._apply(x.contiguous(), bool(adjoint))
+        return op._matvec(x.contiguous(), bool(adjoint))
 
     @staticmethod
     def backward(ctx, dy):
-        return ctx.op._apply(dy.contiguous(), not ctx.adjoint), None, None
+        return ctx.op._matvec(dy.contiguous(), not ctx.adjoint), None, None
+
+
+class LinearOperator(torch.nn.Module):
+    """What the operators of this package share.  A subclass writes `_matvec(x, adjoint)`, the kernel launch (the name stays clear of
+    nn.Module._apply(fn), which .to() / .float() / .cpu() call: those return the operator and move nothing); `forward` / `adjoint` run it
+    through LinearOpFn, so both are differentiable.  One that keeps host arrays also writes `_to_device(device, *key)`, which builds its
+    device tensors: `upload(device, *key)` calls it once per device (and key) and keeps the result, so an upload ahead of a graph capture
+    leaves nothing for the captured iteration to copy."""
+
+    def __init__(self):
+        super().__init__()
+        self._dev = {}
+
+    def forward(self, x):
+        return LinearOpFn.apply(x, self, False)
+
+    def adjoint(self, y):
+        return LinearOpFn.apply(y, self, True)
+
+    def upload(self, device, *key):
+        """The operator's tensors on `device`, copied there at the first call for it."""
+        k = (str(torch.device(device)),) + key if key else str(torch.device(device))
+        t = self._dev.get(k)
+        if t is None:
+            t = self._dev[k] = self._to_device(device, *key)
+        return t
+
+    def _check_patch(self, x, exc, ndim_msg, ndims=(4, 5), nonempty=False):
+        """x is one patch (1, C, T, X[, Y]) with `ndims` axes, raised as the subclass's `exc`; `ndim_msg` takes x.ndim."""
+        name = type(self).__name__
+        if x.ndim not in ndims:
+            raise exc(ndim_msg % x.ndim)
+        if x.shape[0] != 1:
+            raise exc("%s works on one patch at a time: batch size %d" % (name, x.shape[0]))
+        if nonempty and x.numel() < 1:
+            raise exc("%s: empty tensor %s" % (name, tuple(x.shape)))
 
 
 class Chain(torch.nn.Module):

@@ -2,12 +2,12 @@
 import torch
 
 from .. import _lib
-from .base import LinearOpFn
+from .base import LinearOperator
 
 __all__ = ["VerticalGrad", "AxisDerivative"]
 
 
-class AxisDerivative(torch.nn.Module):
+class AxisDerivative(LinearOperator):
     """Finite difference along one axis of an N-d tensor as a linear operator with an exact adjoint (dpi_diff_axis).
     stencil: 'forward' | 'backward' | 'centered' | 'second' (reference utils/processing.py:139-181)."""
     _CODES = {"forward": 0, "backward": 1, "centered": 2, "second": 3}
@@ -18,7 +18,7 @@ class AxisDerivative(torch.nn.Module):
             raise ValueError("Stencil has to be centered, forward or backward")
         self.axis, self.stencil, self.spacing = int(axis), stencil, float(spacing)
 
-    def _apply(self, x, adjoint):
+    def _matvec(self, x, adjoint):
         ax = self.axis % x.ndim
         outer = 1
         for s in x.shape[:ax]:
@@ -29,12 +29,6 @@ class AxisDerivative(torch.nn.Module):
         _lib.check(_lib.load().dpi_diff_axis(_lib.ptr(x), outer, n, inner, self._CODES[self.stencil], self.spacing, int(adjoint),
                                              _lib.ptr(y), _lib.stream()), "dpi_diff_axis")
         return y
-
-    def forward(self, x):
-        return LinearOpFn.apply(x, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)
 
 
 class VerticalGrad(AxisDerivative):

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import LinearOpFn
+from .base import LinearOperator
 
 __all__ = ["Moveout", "check_moveout_table", "MOVEOUT_TAPS", "MOVEOUT_MUTE", "shift_table", "nmo_table", "moveout_ranges"]
 
@@ -147,7 +147,7 @@ def check_moveout_table(table, what="the moveout table"):
     return tab32, live.reshape(tab32.shape)
 
 
-class Moveout(torch.nn.Module):
+class Moveout(LinearOperator):
     """forward: the model (1, C, T, X[, Y]) -> the data of the same shape, d[t] read from row table[t] of its own trace, `interp` =
     "linear" (2 taps) or "cubic" (4 taps, Keys a = -1/2) along t, rows clamped to [0, T - 1]; adjoint: the exact transpose.  `table` is
     (T, X) or (T, X, Y), shared by the channels; a sample is live where 0 <= table <= T - 1 and muted (d = 0) for any other finite value.
@@ -169,22 +169,13 @@ class Moveout(torch.nn.Module):
         self.live = live
         self.T, self.S = T, int(flat.shape[1])
         self._ranges = moveout_ranges(flat, interp)
-        self._dev = {}
 
-    def upload(self, device):
-        """(table, ranges) on `device`, copied there at the first call for it (call it ahead of a graph capture)."""
-        key = str(torch.device(device))
-        t = self._dev.get(key)
-        if t is None:
-            t = (torch.from_numpy(self.table).to(device), torch.from_numpy(self._ranges).to(device))
-            self._dev[key] = t
-        return t
+    def _to_device(self, device):
+        """(table, ranges)"""
+        return torch.from_numpy(self.table).to(device), torch.from_numpy(self._ranges).to(device)
 
-    def _apply(self, x, adjoint):
-        if x.ndim not in (4, 5):
-            raise ValueError("Moveout expects a (1, C, T, X) or (1, C, T, X, Y) tensor, got %d-D" % x.ndim)
-        if x.shape[0] != 1:
-            raise ValueError("Moveout works on one patch at a time: batch size %d" % x.shape[0])
+    def _matvec(self, x, adjoint):
+        self._check_patch(x, ValueError, "Moveout expects a (1, C, T, X) or (1, C, T, X, Y) tensor, got %d-D")
         if tuple(x.shape[2:]) != tuple(self.table.shape) or x.shape[1] < 1:
             raise ValueError("Moveout built from a table of shape %s got a tensor of shape %s: its (T, X[, Y]) must be the table's"
                              % (tuple(self.table.shape), tuple(x.shape)))
@@ -199,9 +190,3 @@ class Moveout(torch.nn.Module):
             _lib.check(L.dpi_moveout_fwd(_lib.ptr(x), _lib.ptr(tau), self.kind, C_, self.T, self.S, _lib.ptr(y), _lib.stream()),
                        "dpi_moveout_fwd")
         return y
-
-    def forward(self, x):
-        return LinearOpFn.apply(x, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import LinearOpFn
+from .base import LinearOperator
 
 __all__ = ["TraceSampling", "check_trace_offsets", "INTERP_TAPS", "interp_weights"]
 
@@ -46,7 +46,7 @@ def interp_weights(offsets, interp):
     return w
 
 
-class TraceSampling(torch.nn.Module):
+class TraceSampling(LinearOperator):
     """forward: (1, C, T, X[, Y]) on the grid -> the same shape at the trace positions; adjoint: its exact transpose.  `offsets` is
     (2, X, Y) — dx, dy per trace in grid cells, |d| <= 0.5 — as numpy array or tensor; a 4-D tensor (1, C, T, X) is the case Y = 1.  The
     offsets are checked here and uploaded once per device.  A tensor whose (X, Y) differs from the offsets and a batch other than 1 raise
@@ -62,24 +62,13 @@ class TraceSampling(torch.nn.Module):
         self.X, self.Y = int(self._off32.shape[1]), int(self._off32.shape[2])
         self.offsets = torch.from_numpy(self._off32)
         self.weights = None if interp == "linear" else torch.from_numpy(interp_weights(self._off32, interp))      # (2, K, X, Y)
-        self._dev = {}
-        self._dev_w = {}
 
-    def upload(self, device):
-        """The offsets on `device`, uploaded at the first call for it (call it ahead of a graph capture, or run one eager iteration); the
-        weight table of a non-linear kind goes with them."""
-        key = str(torch.device(device))
-        if key not in self._dev:
-            self._dev[key] = self.offsets.to(device)
-            if self.weights is not None:
-                self._dev_w[key] = self.weights.to(device)
-        return self._dev[key]
+    def _to_device(self, device):
+        """(offsets, the weight table of a non-linear kind or None)"""
+        return self.offsets.to(device), None if self.weights is None else self.weights.to(device)
 
-    def _apply(self, x, adjoint):
-        if x.ndim not in (4, 5):
-            raise ValueError("TraceSampling works on (1, C, T, X[, Y]) tensors, got %d axes" % x.ndim)
-        if x.shape[0] != 1:
-            raise ValueError("TraceSampling works on one patch at a time: batch size %d" % x.shape[0])
+    def _matvec(self, x, adjoint):
+        self._check_patch(x, ValueError, "TraceSampling works on (1, C, T, X[, Y]) tensors, got %d axes")
         grid = (int(x.shape[3]), int(x.shape[4]) if x.ndim == 5 else 1)
         if grid != (self.X, self.Y):
             raise ValueError("TraceSampling built from offsets of a %d x %d (X, Y) grid got a tensor of %d x %d"
@@ -87,11 +76,10 @@ class TraceSampling(torch.nn.Module):
         C_, T_ = int(x.shape[1]), int(x.shape[2])
         if C_ < 1 or T_ < 1:
             raise ValueError("TraceSampling: empty tensor %s" % (tuple(x.shape),))
-        off = self.upload(x.device)
+        off, w = self.upload(x.device)
         y = torch.empty_like(x)
         L = _lib.load()
-        if self.weights is not None:
-            w = self._dev_w[str(torch.device(x.device))]
+        if w is not None:
             fn, name = ((L.dpi_trace_resample_adj, "dpi_trace_resample_adj") if adjoint
                         else (L.dpi_trace_resample_fwd, "dpi_trace_resample_fwd"))
             _lib.check(fn(_lib.ptr(x), _lib.ptr(w), _lib.ptr(off), INTERP_TAPS[self.interp], C_, T_, self.X, self.Y, _lib.ptr(y),
@@ -100,9 +88,3 @@ class TraceSampling(torch.nn.Module):
         fn, name = (L.dpi_trace_sample_adj, "dpi_trace_sample_adj") if adjoint else (L.dpi_trace_sample_fwd, "dpi_trace_sample_fwd")
         _lib.check(fn(_lib.ptr(x), _lib.ptr(off), C_, T_, self.X, self.Y, _lib.ptr(y), _lib.stream()), name)
         return y
-
-    def forward(self, x):
-        return LinearOpFn.apply(x, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)

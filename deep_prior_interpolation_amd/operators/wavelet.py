@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .base import LinearOpFn
+from .base import LinearOperator
 
 __all__ = ["ConvolutionalModelling", "WAVELET_MODEL_KINDS", "WAVELET_MAX_TAPS"]
 
@@ -13,7 +13,7 @@ WAVELET_MODEL_KINDS = ("reflectivity", "impedance")
 WAVELET_MAX_TAPS = 255
 
 
-class ConvolutionalModelling(torch.nn.Module):
+class ConvolutionalModelling(LinearOperator):
     """forward: (1, C, T, X[, Y]) -> the same shape, every trace filtered along T ('same', zero padded); adjoint: the exact transpose.
         kind = "reflectivity":  d = w * r            taps = w,     no difference      (= 2 VerticalConv(w))
         kind = "impedance":     d = 0.5 w * D m      taps = w / 2, D = the forward difference along T with the last row zero
@@ -41,24 +41,12 @@ class ConvolutionalModelling(torch.nn.Module):
         self.taps = np.ascontiguousarray((w / 2 if self.diff else w).astype(np.float32))          # the one rounding
         if not np.all(np.isfinite(self.taps)) or not np.any(self.taps != 0):
             raise ValueError("the wavelet is all zero (or overflows fp32): nothing would reach the loss")
-        self._dev = {}
 
-    def upload(self, device):
-        """The taps on `device`, copied there at the first call."""
-        key = str(torch.device(device))
-        t = self._dev.get(key)
-        if t is None:
-            t = torch.from_numpy(self.taps).to(device)
-            self._dev[key] = t
-        return t
+    def _to_device(self, device):
+        return torch.from_numpy(self.taps).to(device)
 
-    def _apply(self, x, adjoint):
-        if x.ndim not in (4, 5):
-            raise ValueError("ConvolutionalModelling expects a (1, C, T, X) or (1, C, T, X, Y) tensor, got %d-D" % x.ndim)
-        if x.shape[0] != 1:
-            raise ValueError("ConvolutionalModelling works on one patch at a time: batch size %d" % x.shape[0])
-        if x.numel() < 1:
-            raise ValueError("ConvolutionalModelling: empty tensor %s" % (tuple(x.shape),))
+    def _matvec(self, x, adjoint):
+        self._check_patch(x, ValueError, "ConvolutionalModelling expects a (1, C, T, X) or (1, C, T, X, Y) tensor, got %d-D", nonempty=True)
         C_, T = int(x.shape[1]), int(x.shape[2])
         S = x.numel() // (C_ * T)
         taps = self.upload(x.device)
@@ -67,9 +55,3 @@ class ConvolutionalModelling(torch.nn.Module):
         fn, name = (L.dpi_wavelet_adj, "dpi_wavelet_adj") if adjoint else (L.dpi_wavelet_fwd, "dpi_wavelet_fwd")
         _lib.check(fn(_lib.ptr(x), _lib.ptr(taps), int(self.taps.size), self.diff, C_, T, S, _lib.ptr(y), _lib.stream()), name)
         return y
-
-    def forward(self, x):
-        return LinearOpFn.apply(x, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)

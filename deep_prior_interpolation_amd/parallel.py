@@ -540,6 +540,7 @@ def main(argv=None):
     """Multi-GPU counterpart of main.main(): same flags; each rank optimises the patches it pulls from the shared queue, result
     files are written per patch exactly as in the single-process run, rank 0 additionally saves `reconstructed.npy`."""
     from .data import extract_patches, patch_extractor_for, reassembly_flags
+    from .forward_model import ForwardModel
     from .main import Interpolator
     from .parameter import parse_arguments
     args = parse_arguments(argv)
@@ -602,37 +603,24 @@ def main(argv=None):
         rec = reconstruct_patches(args) if rank == 0 else None
         if rank == 0 and sampler:
             volumes["std"] = reconstruct_patches(args, field="posterior_std")
-        if rank == 0 and getattr(args, "avo_theta", None) is not None:
-            volumes["avo"] = reconstruct_patches(args, field="avo_model")
-    if getattr(args, "wavelet", None) is not None and not sampler and not (getattr(args, "out_ema", 0.0) or 0.0):
-        # --wavelet: the section behind reconstructed.npy, re-assembled on the host from the result files of every rank with the same
-        # windows and weights (--out_ema and the samplers track no model: nothing to re-assemble)
-        if world > 1:
-            dist.barrier()
-        if rank == 0:
-            from .data import reconstruct_patches
-            volumes["model"] = reconstruct_patches(args, field="wavelet_model")
-    if getattr(args, "moveout", None) is not None and not sampler and not (getattr(args, "out_ema", 0.0) or 0.0):
-        # --moveout: the flattened sections behind reconstructed.npy, re-assembled the same way (every patch spans the time axis, so the
-        # windows overlap in x / y only, where the model lives on the data's grid)
-        if world > 1:
-            dist.barrier()
-        if rank == 0:
-            from .data import reconstruct_patches
-            volumes["flat"] = reconstruct_patches(args, field="moveout_model")
+    # the model volumes behind reconstructed.npy (--avo_theta, --wavelet, --moveout), re-assembled on the host from the result files of every
+    # rank with the same windows and weights
+    fields = ForwardModel(args).volumes()
+    if fields and world > 1:
+        dist.barrier()
+    if rank == 0:
+        from .data import reconstruct_patches
+        for field, name in fields:
+            volumes[name] = reconstruct_patches(args, field=field)
     _print_holdout_summary(rank, holdout_snrs)
     if rank == 0:
         np.save(os.path.join(outpath, "reconstructed.npy"), rec)
-        if volumes.get("flat") is not None:
-            np.save(os.path.join(outpath, "reconstructed_flat.npy"), volumes["flat"])
-        if volumes.get("model") is not None:
-            np.save(os.path.join(outpath, "reconstructed_model.npy"), volumes["model"])
+        for _, name in fields:
+            if volumes[name] is not None:
+                np.save(os.path.join(outpath, name), volumes[name])
         if sampler and volumes.get("std") is not None:
             # the window-weighted mean of the per-patch posterior variances, as a std: the spread WITHIN the windows
             np.save(os.path.join(outpath, "reconstructed_std.npy"), volumes["std"])
-        if volumes.get("avo") is not None:
-            # --avo_theta: the three parameter sections (T', X', 3) behind reconstructed.npy, re-assembled with the same windows
-            np.save(os.path.join(outpath, "reconstructed_avo.npy"), volumes["avo"])
         print("rank 0: %d patches total, %d local; reconstructed volume %s saved" % (len(patches), len(mine), rec.shape))
     if world > 1:
         dist.destroy_process_group()

@@ -357,30 +357,22 @@ def parse_arguments(argv=None) -> Namespace:
     return postprocess(build_parser().parse_args(argv))
 
 
+_same = lambda v: v
+# (key, what an args.txt without the key means, normaliser): what the network's output means and what its weights were fitted through
+_OURS_MUST_MATCH = (
+    ("avo_theta", None, lambda t: None if t is None else [float(x) for x in t]),       # the network's output channels
+    ("trace_offsets", None, _same), ("trace_interp", "linear", _same),
+    ("wavelet", None, _same), ("wavelet_model", "reflectivity", _same),
+    ("moveout", None, _same), ("moveout_interp", "linear", _same),
+)
+
+
 def net_args_are_same(args1: Namespace, args2: Namespace) -> bool:
     """Compatibility of a saved args.txt with the current run before loading its weights (parameter.py:133-173)."""
     a, b = vars(args1), vars(args2)
     errors = [k for k in _MUST_MATCH if a[k] != b[k]]
-    # --avo_theta (ours) decides the network's output channels and what they mean; args.txt files of older runs lack the key: off
-    ta, tb = a.get("avo_theta"), b.get("avo_theta")
-    if (None if ta is None else [float(t) for t in ta]) != (None if tb is None else [float(t) for t in tb]):
-        errors.append("avo_theta")
-    # --trace_offsets (ours) decides what the weights were fitted to; args.txt files of older runs lack the key: off
-    if a.get("trace_offsets") != b.get("trace_offsets"):
-        errors.append("trace_offsets")
-    # --trace_interp (ours) decides the operator the weights were fitted through; an args.txt without the key: linear
-    if (a.get("trace_interp") or "linear") != (b.get("trace_interp") or "linear"):
-        errors.append("trace_interp")
-    # --wavelet / --wavelet_model (ours) decide what the network's output means; an args.txt without the keys: off / reflectivity
-    if a.get("wavelet") != b.get("wavelet"):
-        errors.append("wavelet")
-    if (a.get("wavelet_model") or "reflectivity") != (b.get("wavelet_model") or "reflectivity"):
-        errors.append("wavelet_model")
-    # --moveout / --moveout_interp (ours) decide what the network's output means; an args.txt without the keys: off / linear
-    if a.get("moveout") != b.get("moveout"):
-        errors.append("moveout")
-    if (a.get("moveout_interp") or "linear") != (b.get("moveout_interp") or "linear"):
-        errors.append("moveout_interp")
+    # ours: args.txt files of older runs lack these keys, which then count as the default (off, or the named kind)
+    errors += [k for k, default, norm in _OURS_MUST_MATCH if norm(a.get(k) or default) != norm(b.get(k) or default)]
     warns = [k for k in _OVERRIDDEN if a[k] != b[k]]
     if errors:
         print("The following arguments keys have to be the same:\n\t")

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..operators.base import LinearOpFn
+from ..operators.base import LinearOperator
 from .processing import GaussianFilter, gaussian_kernel
 
 __all__ = ["Hale2D", "Hale2DSections", "directional_laplacian", "structure_tensor_dips", "structure_tensor_dips_sections"]
@@ -103,7 +103,7 @@ def structure_tensor_dips(in_content: torch.Tensor, dv: float = 1., dh: float = 
         return phi, aniso
 
 
-class Hale2D(torch.nn.Module):
+class Hale2D(LinearOperator):
     """Directional Laplacian built on a dip field (BCHW, same shape as the sections it is applied to) — slopes.py:72-105.
     forward(x) = -(Dh(a Dv x + b Dh x) + Dv(b Dv x + c Dh x)) with a = cos^2, b = -cos sin, c = sin^2; differentiable (the
     backward is the exact transpose kernel), plus an explicit `adjoint` the reference does not have."""
@@ -118,7 +118,7 @@ class Hale2D(torch.nn.Module):
             self.c = (u2 * u2).contiguous()
             self.dips = directions
 
-    def _apply(self, x, adjoint):
+    def _matvec(self, x, adjoint):
         x, N, H, W = _planes(x)
         if tuple(x.shape) != tuple(self.a.shape):
             raise _lib.DpiError("Hale2D: tensor shape %s differs from the dip field %s" % (tuple(x.shape), tuple(self.a.shape)))
@@ -127,18 +127,12 @@ class Hale2D(torch.nn.Module):
                                           _lib.ptr(y), _lib.stream()), "dpi_hale2d")
         return y
 
-    def forward(self, inputs):
-        return LinearOpFn.apply(inputs, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)
-
 
 def directional_laplacian(in_content: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
     return Hale2D(theta)(in_content)
 
 
-class Hale2DSections(torch.nn.Module):
+class Hale2DSections(LinearOperator):
     """Hale2D on both families of vertical sections of a (B,C,T,X,Y) patch: forward(x) = stack(L_tx x, L_ty x) of shape (2,B,C,T,X,Y),
     with L_tx = Hale2D(phi_tx) on every (t,x) section (v = t, h = x) and L_ty = Hale2D(phi_ty) on every (t,y) section (v = t, h = y).
     adjoint(g) = L_tx^T g[0] + L_ty^T g[1].  Differentiable (the backward is the transpose kernel); `dips` is (2, B*C, T, X, Y)."""
@@ -157,7 +151,7 @@ class Hale2DSections(torch.nn.Module):
             # [a, b, c] of the (t,x) family, then of the (t,y) family
             self.coef = torch.stack((u1[0] * u1[0], u1[0] * u2[0], u2[0] * u2[0], u1[1] * u1[1], u1[1] * u2[1], u2[1] * u2[1])).contiguous()
 
-    def _apply(self, x, adjoint):
+    def _matvec(self, x, adjoint):
         if not x.is_cuda or x.dtype != torch.float32:
             raise _lib.DpiError("slopes operators run on fp32 GPU tensors (no CPU path)")
         if not self.coef.is_cuda or self.coef.device != x.device:
@@ -171,9 +165,3 @@ class Hale2DSections(torch.nn.Module):
         _lib.check(_lib.load().dpi_hale_sections(_lib.ptr(x), _lib.ptr(self.coef), B * C, T, X, Y, int(adjoint), _lib.ptr(y), _lib.stream()),
                    "dpi_hale_sections")
         return y
-
-    def forward(self, inputs):
-        return LinearOpFn.apply(inputs, self, False)
-
-    def adjoint(self, y):
-        return LinearOpFn.apply(y, self, True)

@@ -66,13 +66,13 @@ def test_operator_refusals():
     op = AVOLinearModelling([0, 10, 20, 30], nt0=6, spatdims=(5,))
     # refused from the shapes alone, before the library is even looked up (these are host tensors)
     with pytest.raises(_lib.DpiError, match="batch"):
-        op._apply(torch.zeros(2, 3, 6, 5), False)
+        op._matvec(torch.zeros(2, 3, 6, 5), False)
     with pytest.raises(_lib.DpiError, match="nt0"):
-        op._apply(torch.zeros(1, 3, 7, 5), False)
+        op._matvec(torch.zeros(1, 3, 7, 5), False)
     with pytest.raises(_lib.DpiError, match="channels"):
-        op._apply(torch.zeros(1, 3, 6, 5), True)
+        op._matvec(torch.zeros(1, 3, 6, 5), True)
     with pytest.raises(_lib.DpiError, match="spatial"):
-        op._apply(torch.zeros(1, 3, 6, 5, 2), False)
+        op._matvec(torch.zeros(1, 3, 6, 5, 2), False)
     with pytest.raises(_lib.DpiError):                       # no CPU path
         op.forward(torch.zeros(1, 3, 6, 5))
 

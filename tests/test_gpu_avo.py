@@ -202,7 +202,7 @@ def test_loop_eager_and_graph(tmp_path):
         out, model = run["output"], run["avo_model"]
         assert out.shape == (32, 32, 5) and model.shape == (32, 32, 3) and model.dtype == np.float32
         # G m reproduces the output within the recovery bound, per (t, x): 8 cond(G_t) 2^-24 |m|
-        G = T._avo_op.G.numpy().reshape(5, 3, 32).astype(np.float64)
+        G = T.forward_model.stage("avo").op.G.numpy().reshape(5, 3, 32).astype(np.float64)
         back = np.einsum("akt,txk->txa", G, model.astype(np.float64))
         cond = np.array([np.linalg.cond(G[:, :, t]) for t in range(32)])
         err = np.linalg.norm(back - out.astype(np.float64), axis=-1)
@@ -250,7 +250,7 @@ def test_without_the_flag_nothing_changes(golden, tmp_path):
     T = Interpolator(a, str(tmp_path))
     T.load_data({"image": g["image"], "mask": g["mask"], "name": "0"})
     T.build_model()
-    assert T.avo is None and T.net_outchannel() == 3 == g["image"].shape[-1]
+    assert T.forward_model.stage("avo") is None and T.net_outchannel() == 3 == g["image"].shape[-1]
     T.net.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in g["init_state"].items()})
     T.net.to(DEV)
     T.input_ = torch.from_numpy(np.array(g["z"], dtype=np.float32)).to(DEV)
@@ -261,7 +261,7 @@ def test_without_the_flag_nothing_changes(golden, tmp_path):
     assert np.argmin(T.history.loss) == np.argmin(g["loss"])
     ref = np.asarray(g["out_best"], np.float64)
     assert T.out_best.shape == ref.shape and np.linalg.norm(T.out_best - ref) < 1e-2 * np.linalg.norm(ref)
-    assert T._avo_op is None
+    assert T.forward_model.stage("avo") is None
     T.save_result()
     run = np.load(tmp_path / "0_run.npy", allow_pickle=True).item()
     assert not any(k.startswith("avo") for k in run)

@@ -250,7 +250,7 @@ def _model_reproduces_output(T, run, is_3d, what):
     samples of the output are exactly 0 and are out of the device mask, so they carry no loss."""
     out, model, table, interp = run["output"], run["moveout_model"], run["moveout"], run["moveout_interp"]
     assert model is not None and model.shape == out.shape and model.dtype == np.float32 and np.isfinite(model).all()
-    assert table.dtype == np.float32 and table.shape == out.shape[:table.ndim] and np.array_equal(table, T._moveout_op.table)
+    assert table.dtype == np.float32 and table.shape == out.shape[:table.ndim] and np.array_equal(table, T.forward_model.stage("moveout").op.table)
     dev = (lambda v: v[None, None]) if is_3d else (lambda v: np.moveaxis(v, -1, 0)[None])
     flat = lambda v: dev(v).reshape(1, -1, table.shape[0], table[0].size)
     ref, mag = M.forward64(flat(model), table.reshape(table.shape[0], -1), interp)
@@ -258,7 +258,7 @@ def _model_reproduces_output(T, run, is_3d, what):
     bound = M.fwd_bound(interp, mag)
     print("%s: worst |L(model) - output| / bound = %.3f" % (what, float((err / np.maximum(bound, 1e-300)).max())))
     assert np.all(err <= bound) and np.abs(ref).max() > 0
-    live = T._moveout_op.live
+    live = T.forward_model.stage("moveout").op.live
     assert 0 < live.mean() < 1 and np.array_equal(live, (table >= 0) & (table <= table.shape[0] - 1))
     muted = np.broadcast_to(~live.reshape(flat(out).shape[2:])[None, None], flat(out).shape)
     assert not flat(out)[muted].any()
@@ -291,7 +291,7 @@ def test_the_identity_table_reproduces_the_run_without_the_flag(tmp_path, mode, 
     those of the run without the flag bit for bit — and the model is the output."""
     T0, run0 = _run(tmp_path, "3d", mode, None, epochs=6)
     T1, run1 = _run(tmp_path, "3d", mode, "identity", interp, epochs=6)
-    assert T0._moveout_op is None and T1._moveout_op is not None and T1._moveout_op.live.all() and len(T1.history.loss) == 6
+    assert T0.forward_model.stage("moveout") is None and T1.forward_model.stage("moveout").op is not None and T1.forward_model.stage("moveout").op.live.all() and len(T1.history.loss) == 6
     for a, b in zip(_history(T0), _history(T1)):
         np.testing.assert_array_equal(a, b)
     assert np.array_equal(run0["output"], run1["output"])
@@ -304,7 +304,7 @@ def test_loop_with_holdout_draws_no_muted_sample(tmp_path, mode):
     T, run = _run(tmp_path, "2d", mode, "nmo", extra=("--holdout", "0.2"))
     assert len(T.history.loss) == 4 and run["holdout"] is not None and run["best_iter"] == T.best_iter
     _model_reproduces_output(T, run, False, "holdout " + mode)
-    live, sel = T._moveout_op.live, T.holdout_sel                # (T, X), (X, C)
+    live, sel = T.forward_model.stage("moveout").op.live, T.holdout_sel                # (T, X), (X, C)
     assert sel.sum() > 0
     held = T.mask_.cpu().numpy()[0] * np.moveaxis(sel, -1, 0)[:, None]          # (C, T, X): the samples the validation misfit sees
     assert held.sum() > 0 and not held[:, ~live].any()

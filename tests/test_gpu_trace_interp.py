@@ -261,7 +261,7 @@ def _history(T):
 def test_a_file_of_zeros_reproduces_the_run_without_either_flag(tmp_path, mode):
     T0, run0 = _run(tmp_path, mode, None)
     T1, run1 = _run(tmp_path, mode, "zero", "sinc8")
-    assert T0._sampling_op is None and T1._sampling_op.interp == "sinc8" and len(T1.history.loss) == EPOCHS
+    assert T0.forward_model.stage("sampling") is None and T1.forward_model.stage("sampling").op.interp == "sinc8" and len(T1.history.loss) == EPOCHS
     for a, b in zip(_history(T0), _history(T1)):
         np.testing.assert_array_equal(a, b)                               # bit for bit
     np.testing.assert_array_equal(T0.out_best, T1.out_best)
@@ -282,7 +282,7 @@ def test_random_offsets_eager_and_graph_and_what_is_saved(tmp_path, interp):
     np.testing.assert_allclose(res["graph"][0][3], res["eager"][0][3], rtol=1e-7)
     np.testing.assert_array_equal(res["graph"][1], res["eager"][1])
     # T is the graph run
-    assert run["trace_interp"] == interp and T._sampling_op.interp == interp
+    assert run["trace_interp"] == interp and T.forward_model.stage("sampling").op.interp == interp
     np.testing.assert_array_equal(run["output"], T.out_best)
     grid = T._out_best_dev.detach().float().reshape(T.img_.shape)
     sampled = T.data_forward(grid).cpu().numpy()[0, 0]
@@ -295,7 +295,7 @@ def test_the_default_is_the_bilinear_operator(tmp_path):
     """--trace_offsets alone and with --trace_interp linear spelled out: the same run bit for bit, through the bilinear entry points."""
     T0, run0 = _run(tmp_path, "eager", "random")
     T1, run1 = _run(tmp_path, "eager", "random", "linear")
-    assert T0._sampling_op.interp == T1._sampling_op.interp == "linear" and T0._sampling_op.weights is None
+    assert T0.forward_model.stage("sampling").op.interp == T1.forward_model.stage("sampling").op.interp == "linear" and T0.forward_model.stage("sampling").op.weights is None
     for a, b in zip(_history(T0), _history(T1)):
         np.testing.assert_array_equal(a, b)
     np.testing.assert_array_equal(T0.out_best, T1.out_best)

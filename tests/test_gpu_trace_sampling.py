@@ -200,7 +200,7 @@ def _history(T):
 def test_a_file_of_zeros_reproduces_the_run_without_the_flag(tmp_path, mode):
     T0, run0 = _run(tmp_path, mode, None)
     T1, run1 = _run(tmp_path, mode, "zero")
-    assert T0._sampling_op is None and T1._sampling_op is not None and len(T1.history.loss) == EPOCHS
+    assert T0.forward_model.stage("sampling") is None and T1.forward_model.stage("sampling").op is not None and len(T1.history.loss) == EPOCHS
     for a, b in zip(_history(T0), _history(T1)):
         np.testing.assert_array_equal(a, b)                               # bit for bit
     np.testing.assert_array_equal(T0.out_best, T1.out_best)

@@ -295,7 +295,7 @@ def test_the_unit_wavelet_reproduces_the_run_without_the_flag(tmp_path, mode):
     those of the run without the flag bit for bit — and the model is the output."""
     T0, run0 = _run(tmp_path, "3d", mode, None, epochs=6)
     T1, run1 = _run(tmp_path, "3d", mode, np.array([1.0]), epochs=6)
-    assert T0._wavelet_op is None and T1._wavelet_op is not None and len(T1.history.loss) == 6
+    assert T0.forward_model.stage("wavelet") is None and T1.forward_model.stage("wavelet").op is not None and len(T1.history.loss) == 6
     for a, b in zip(_history(T0), _history(T1)):
         np.testing.assert_array_equal(a, b)
     np.testing.assert_array_equal(run0["output"], run1["output"])
@@ -315,7 +315,7 @@ def test_without_the_flag_nothing_changes(golden, tmp_path):
     T = Interpolator(a, str(tmp_path))
     T.load_data({"image": g["image"], "mask": g["mask"], "name": "0"})
     T.build_model()
-    assert T.wavelet is None and T._wavelet_op is None and T.net_outchannel() == g["image"].shape[-1]
+    assert T.forward_model.stage("wavelet") is None and T.net_outchannel() == g["image"].shape[-1]
     T.net.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in g["init_state"].items()})
     T.net.to(DEV)
     T.input_ = torch.from_numpy(np.array(g["z"], dtype=np.float32)).to(DEV)
@@ -326,7 +326,7 @@ def test_without_the_flag_nothing_changes(golden, tmp_path):
     assert np.argmin(T.history.loss) == np.argmin(g["loss"])
     ref = np.asarray(g["out_best"], np.float64)
     assert T.out_best.shape == ref.shape and np.linalg.norm(T.out_best - ref) < 1e-2 * np.linalg.norm(ref)
-    assert T._wavelet_best is None and T.wavelet_model() is None
+    assert T.forward_model.best is None and T.wavelet_model() is None
     T.save_result()
     run = np.load(tmp_path / "0_run.npy", allow_pickle=True).item()
     assert not any(k.startswith("wavelet") for k in run)

@@ -180,13 +180,13 @@ def test_operator_refuses_interp_batch_and_shape():
     op = Moveout(np.zeros((6, 5)))
     # refused from the shape alone, before the library is even looked up (these are host tensors)
     with pytest.raises(ValueError, match="batch"):
-        op._apply(torch.zeros(2, 1, 6, 5), False)
+        op._matvec(torch.zeros(2, 1, 6, 5), False)
     with pytest.raises(ValueError, match="table"):
-        op._apply(torch.zeros(1, 1, 6, 4), False)
+        op._matvec(torch.zeros(1, 1, 6, 4), False)
     with pytest.raises(ValueError, match="table"):
-        op._apply(torch.zeros(1, 1, 6, 5, 1), True)
+        op._matvec(torch.zeros(1, 1, 6, 5, 1), True)
     with pytest.raises(ValueError):
-        op._apply(torch.zeros(1, 6, 5), False)
+        op._matvec(torch.zeros(1, 6, 5), False)
     with pytest.raises(_lib.DpiError):                           # no CPU path
         op.forward(torch.zeros(1, 1, 6, 5))
     op3 = Moveout(torch.zeros(6, 5, 2), interp="cubic")
@@ -322,7 +322,7 @@ def test_load_data_takes_muted_samples_out_of_the_device_mask(tmp_path):
     mask[:, 0, 0] = 1.0
     std = T.load_data({"image": img, "mask": mask, "name": "0", "moveout": table})
     live = table >= 0
-    assert np.array_equal(T._moveout_op.live, live) and np.array_equal(T.mask, mask)             # the host mask stays the file's
+    assert np.array_equal(T.forward_model.stage("moveout").op.live, live) and np.array_equal(T.mask, mask)             # the host mask stays the file's
     assert np.array_equal(T.mask_[0, 0].numpy(), (mask[..., 0] * live).astype(np.float32)) and std > 0
     assert np.array_equal(T.known_mask(), mask * live[..., None])
     T.begin_patch(0)
@@ -342,7 +342,7 @@ def test_load_data_takes_muted_samples_out_of_the_device_mask(tmp_path):
     with pytest.raises(ValueError, match="--moveout is off"):
         T0.load_data({"image": img, "mask": mask, "name": "0", "moveout": table})
     T0.load_data({"image": img, "mask": mask, "name": "0"})
-    assert T0._moveout_op is None and T0.known_mask() is T0.mask and T0.moveout_model() is None
+    assert T0.forward_model.stage("moveout") is None and T0.known_mask() is T0.mask and T0.moveout_model() is None
 
 
 def test_interpolator_refuses_what_the_parser_refuses():

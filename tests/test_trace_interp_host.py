@@ -207,11 +207,11 @@ def test_operator_refusals_and_attributes():
         assert op.interp == name and op.offsets.dtype == torch.float32 and tuple(op.offsets.shape) == (2, 5, 7)
         assert tuple(op.weights.shape) == (2, TAPS[name], 5, 7) and np.array_equal(op.weights.numpy(), interp_weights(off, name))
         with pytest.raises(ValueError, match="5 x 7"):                  # a foreign grid, refused from the shapes alone
-            op._apply(torch.zeros(1, 2, 3, 7, 5), False)
+            op._matvec(torch.zeros(1, 2, 3, 7, 5), False)
         with pytest.raises(ValueError, match="5 x 7"):
-            op._apply(torch.zeros(1, 2, 3, 5), True)
+            op._matvec(torch.zeros(1, 2, 3, 5), True)
         with pytest.raises(ValueError, match="batch"):
-            op._apply(torch.zeros(2, 2, 3, 5, 7), False)
+            op._matvec(torch.zeros(2, 2, 3, 5, 7), False)
     for bad in ("sinc6", "nearest", None, 2):
         with pytest.raises(ValueError, match="interpolation"):
             TraceSampling(off, interp=bad)

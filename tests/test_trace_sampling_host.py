@@ -66,11 +66,11 @@ def test_operator_refusals():
     assert op.offsets.dtype == torch.float32 and tuple(op.offsets.shape) == (2, 5, 7)
     # refused from the shapes alone, before the library is even looked up (these are host tensors)
     with pytest.raises(ValueError, match="5 x 7"):
-        op._apply(torch.zeros(1, 2, 3, 7, 5), False)
+        op._matvec(torch.zeros(1, 2, 3, 7, 5), False)
     with pytest.raises(ValueError, match="5 x 7"):
-        op._apply(torch.zeros(1, 2, 3, 5), True)                       # a 4-D tensor is Y = 1
+        op._matvec(torch.zeros(1, 2, 3, 5), True)                       # a 4-D tensor is Y = 1
     with pytest.raises(ValueError, match="batch"):
-        op._apply(torch.zeros(2, 2, 3, 5, 7), False)
+        op._matvec(torch.zeros(2, 2, 3, 5, 7), False)
     bad = offsets_for("random", 5, 7)
     bad[1, 2, 3] = np.nan
     with pytest.raises(ValueError, match="non-finite"):

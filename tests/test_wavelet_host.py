@@ -83,8 +83,8 @@ def test_interpolator_names_the_flag_for_a_bad_file(tmp_path):
         Interpolator(parse_arguments(["--imgdir", str(tmp_path), "--wavelet", "missing.npy"]), "/tmp", device="cpu")
     T = Interpolator(parse_arguments(["--imgdir", str(tmp_path), "--wavelet", "good.npy", "--wavelet_model", "impedance"]), "/tmp",
                      device="cpu")
-    assert T._wavelet_op.kind == "impedance" and T._wavelet_op.taps.size == 9 and T.wavelet_model() is None
-    assert Interpolator(parse_arguments(["--imgdir", str(tmp_path)]), "/tmp", device="cpu")._wavelet_op is None
+    assert T.forward_model.stage("wavelet").op.kind == "impedance" and T.forward_model.stage("wavelet").op.taps.size == 9 and T.wavelet_model() is None
+    assert Interpolator(parse_arguments(["--imgdir", str(tmp_path)]), "/tmp", device="cpu").forward_model.stage("wavelet") is None
 
 
 # ---------------------------------------------------------------- operator --------------------------------------------------------
@@ -101,11 +101,11 @@ def test_operator_refuses_kind_and_batch():
     op = ConvolutionalModelling(np.ones(3))
     # refused from the shape alone, before the library is even looked up (these are host tensors)
     with pytest.raises(ValueError, match="batch"):
-        op._apply(torch.zeros(2, 1, 6, 5), False)
+        op._matvec(torch.zeros(2, 1, 6, 5), False)
     with pytest.raises(ValueError, match="batch"):
-        op._apply(torch.zeros(3, 1, 6, 5, 2), True)
+        op._matvec(torch.zeros(3, 1, 6, 5, 2), True)
     with pytest.raises(ValueError):
-        op._apply(torch.zeros(1, 6, 5), False)
+        op._matvec(torch.zeros(1, 6, 5), False)
     with pytest.raises(_lib.DpiError):                           # no CPU path
         op.forward(torch.zeros(1, 1, 6, 5))
     assert ConvolutionalModelling(np.ones(255)).taps.size == 255

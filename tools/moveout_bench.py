@@ -45,7 +45,7 @@ def main():
             op = Moveout(tab, interp)
             op.upload("cuda")
             for adjoint in (False, True):
-                variants["%s_%s_%s" % (tname, interp, "adj" if adjoint else "fwd")] = (lambda op=op, adjoint=adjoint: op._apply(x, adjoint),
+                variants["%s_%s_%s" % (tname, interp, "adj" if adjoint else "fwd")] = (lambda op=op, adjoint=adjoint: op._matvec(x, adjoint),
                                                                                      float(op.live.mean()))
     variants["copy"] = (lambda: y.copy_(x), 1.0)
 
