@@ -141,6 +141,10 @@ SIGNATURES = {
     # [2][T][S] int32, interp 0 = linear, 1 = cubic.  ABI_VERSION stays: a stale library fails on the unresolved symbols
     "dpi_moveout_fwd": (_I, [_P, _P, _I, _I, _I, _Z, _P, _P]),
     "dpi_moveout_adj": (_I, [_P, _P, _P, _I, _I, _I, _Z, _P, _P]),
+    # --model_reg (ours): (n) and (m, C, n0, n1, n2, axes, grad, ws, res, stream); m / grad = [C][n0][n1][n2] fp32, bit k of axes = differences
+    # along n_k, 0 = plain L1, res = double[1].  ABI_VERSION stays: a stale library fails on the unresolved symbols
+    "dpi_model_reg_ws_doubles": (_Z, [_Z]),
+    "dpi_model_reg": (_I, [_P, _I, _Z, _Z, _Z, _I, _P, _P, _P, _P]),
     # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -18,7 +18,7 @@ from .data import extract_patches
 from .forward_model import ForwardModel, to_numpy_out
 from .loop import LoopRule
 from .optim import DevicePlateau, FusedAdam, FusedLangevin, posterior_sample_count
-from .parameter import check_out_ema, net_args_are_same, parse_arguments
+from .parameter import check_model_reg, check_out_ema, net_args_are_same, parse_arguments
 
 warnings.filterwarnings("ignore")
 
@@ -50,6 +50,10 @@ class Interpolator:
         # --avo_theta, --wavelet, --moveout, --trace_offsets (ours): the operators between the network and the loss (net_forward,
         # data_forward) and what is kept of them for the selected output
         self.forward_model = ForwardModel(args)
+        # --model_reg (ours): None, or (kind, weight, dims) of the penalty on the tensor the network itself writes, and that tensor of
+        # the current iteration with its graph (net_forward)
+        self.model_reg = check_model_reg(args)
+        self._net_out = None
         # --optimizer sgld | psgld (ours): Langevin sampling; Namespaces of reference args.txt files lack the keys
         self.optimizer_kind = getattr(args, "optimizer", "adam")
         if self.optimizer_kind not in ("adam", "sgld", "psgld"):
@@ -283,7 +287,12 @@ class Interpolator:
         iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
         them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m); with --moveout the network writes
         the flattened gather and the moveout operator comes last (d = L m): what this returns is a data-domain tensor either way."""
-        return self.forward_model.apply_model(self._net_forward(z))
+        m = self._net_forward(z)
+        if self.model_reg is not None:
+            # --model_reg: what the network wrote is kept with its graph until model_regularization() takes it.  Without the flag nothing
+            # is kept: a tensor that outlives the iteration would change what is alive while an iteration is captured
+            self._net_out = m
+        return self.forward_model.apply_model(m)
 
     def _net_forward(self, z):
         if getattr(self.args, "net", "multiunet") != "part":
@@ -482,16 +491,21 @@ class Interpolator:
             self.input_list.append(u.torch_to_np(input_, True))
         out_, ema, total_loss, metrics = self._forward_and_loss(input_)
         reg = self.regularization(out_, total_loss)          # None, or (weight tensor / float, reg loss) of a subclass / add-on
+        mreg = self.model_regularization()                   # None, or (weight, R(m)) of --model_reg
         total = total_loss if reg is None else total_loss + reg[0] * reg[1]
+        if mreg is not None:
+            total = total + mreg[0] * mreg[1]
         total.backward()
         ops.finish_backward(self._grad_params())
         m, em = self._read_back(metrics, ema)                  # one read-back
         l, s, p = m[:3]
-        if reg is None:
+        if reg is None and mreg is None:
             self.history.append((l, s, p))
         else:
             main_l, l = l, float(total.item())                 # the loop follows the total
-            self.history.append((l, main_l, float(reg[1].item()), s, p))          # HistoryReg layout (main_pocs.py:198-202)
+            self.history.append((l, main_l, 0.0 if reg is None else float(reg[1].item()), s, p))          # HistoryReg layout (main_pocs.py:198-202)
+            if mreg is not None:
+                self.history.append_model_reg(float(mreg[1].item()))
         self.history.lr.append(self.optimizer.param_groups[0]["lr"])
         # the rule of csrc/loop_rule.h on the doubles of the same read-back: the raw columns and minima as ever, the selection on q —
         # decided before a minimum is written, as q's minimum may be loss_min / val_min itself
@@ -553,6 +567,15 @@ class Interpolator:
             # one loss pass over [L_tx out, L_ty out]: both halves have C*T*X*Y samples, so the sum of their two means is twice the mean
             reg_loss = 2.0 * reg_loss
         return float(self.args.aa_weight), reg_loss
+
+    def model_regularization(self):
+        """--model_reg: None, or (W, R) with R = ops.model_reg of the tensor the network wrote in this iteration (net_forward), before
+        any operator of the forward model: plain L1 or total variation along the flag's axes, divided by the element count."""
+        if self.model_reg is None:
+            return None
+        _, weight, dims = self.model_reg
+        m, self._net_out = self._net_out, None
+        return weight, ops.model_reg(m, dims)
 
     def build_regularizer(self):
         """Anti-aliasing add-on (BASELINE configs[3]; the reference ships the operators — utils/slopes.py, operators/ — but no
@@ -620,6 +643,9 @@ class Interpolator:
         start = time()
         if mode == "graph" and self.noise_source() != "philox":
             raise ValueError("--noise_source torch_cpu draws on the host every iteration: it cannot be captured (mode='eager')")
+        if mode == "graph" and self.model_reg is not None:
+            raise ValueError("--model_reg %s cannot be captured (mode='eager'): the captured iteration evaluates no regulariser, and the "
+                             "term must not be dropped silently" % self.model_reg[0])
         if mode == "graph":
             self._optimize_graph(verbose, check_every)
         else:
@@ -666,6 +692,9 @@ class Interpolator:
         a = self.args
         if self.noise_source() != "philox":
             raise ValueError("--noise_source torch_cpu draws on the host every iteration: it cannot be captured into a graph")
+        if self.model_reg is not None:
+            raise ValueError("--model_reg %s cannot be captured into a graph (mode='eager'): the captured iteration evaluates no "
+                             "regulariser, and the term must not be dropped silently" % self.model_reg[0])
         L = _lib.load()
         dev = self.device
         if self.optimizer is None:
@@ -752,7 +781,7 @@ class Interpolator:
         self.graph_finish()
 
     def has_regularizer(self):
-        return getattr(self, "_aa_op", None) is not None
+        return getattr(self, "_aa_op", None) is not None or self.model_reg is not None
 
     def _eager_reasons(self, net_inputs=None):
         """Why the loaded patch is optimised eagerly instead of from a captured iteration: each reason once, for optimize(mode='auto')
@@ -785,6 +814,8 @@ class Interpolator:
             run["out_ema"] = self.out_ema                        # `output` is the selected running average, best_iter its iteration
             run["best_iter"] = self.best_iter
         run.update(self.forward_model.run_fields(self._optimised_output()))
+        if self.model_reg is not None:
+            run.update(model_reg=self.model_reg[0], model_reg_weight=self.model_reg[1])
         if self.is_sampler():
             run.update(posterior_std=self.posterior_std, posterior_samples=self.posterior_samples, output_selected=self.output_selected,
                        posterior_snr=self.posterior_snr, posterior_val_snr=self.posterior_val_snr)
@@ -798,13 +829,15 @@ class Interpolator:
         self.best_iter = self.val_min = self.ema_min = None
         self._out_best_dev = None
         self.forward_model.clean()
+        self._net_out = None
         self._ema_avg = self._ema_best = None                    # the running average belongs to the patch
         self._reset_posterior()
         self._zero_moments()
         self.history = self._new_history()
 
     def _new_history(self):
-        return u.history_class(self.has_regularizer(), self.holdout > 0.0, self.out_ema > 0.0)(self.args.epochs)
+        return u.history_class(self.has_regularizer(), self.holdout > 0.0, self.out_ema > 0.0,
+                               model_reg=self.model_reg is not None)(self.args.epochs)
 
 
 def optimize_concurrently(Ts, check_every=64, prepare=None, timings=None):

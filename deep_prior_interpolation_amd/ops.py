@@ -1359,6 +1359,37 @@ class MaskedLossHoldoutFn(torch.autograd.Function):
         return dout * gloss, None, None, None, None
 
 
+class ModelRegFn(torch.autograd.Function):
+    """--model_reg: R(m) = plain L1 (no dims) or anisotropic total variation along `dims` of the device tensor m = (1, C, n0, n1[, n2]),
+    divided by m.numel(); value and gradient from one launch (dpi_model_reg).  Returns R as an fp32 scalar."""
+
+    @staticmethod
+    def forward(ctx, m, dims):
+        if not m.is_contiguous():
+            raise _lib.DpiError("model_reg: the tensor must be contiguous")
+        m = _req(m, "model_reg tensor")
+        if m.ndim not in (4, 5) or m.shape[0] != 1 or m.numel() == 0:
+            raise _lib.DpiError("model_reg: expected (1, C, n0, n1[, n2]), got %s" % (tuple(m.shape),))
+        dims = sorted(set(int(d) for d in dims))
+        if any(d < 2 or d >= m.ndim for d in dims):
+            raise _lib.DpiError("model_reg: dims %s of a tensor %s: channels are never differenced" % (dims, tuple(m.shape)))
+        # (1, C, a, b) is [C][1][a][b]: the fastest axis stays n2, the one the kernel vectorises along
+        ext = (1,) * (5 - m.ndim) + tuple(m.shape[2:])
+        axes = sum(1 << (d - 2 + 5 - m.ndim) for d in dims)
+        L = _lib.load()
+        ws = torch.empty(L.dpi_model_reg_ws_doubles(m.numel()), dtype=torch.float64, device=m.device)
+        res = torch.empty(1, dtype=torch.float64, device=m.device)
+        grad = torch.empty_like(m)
+        check(L.dpi_model_reg(ptr(m), m.shape[1], ext[0], ext[1], ext[2], axes, ptr(grad), ptr(ws), ptr(res), stream()), "dpi_model_reg")
+        ctx.save_for_backward(grad)
+        return res[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (grad,) = ctx.saved_tensors
+        return grad * gloss, None
+
+
 class MaxPool2x2Fn(torch.autograd.Function):
     """nn.MaxPool2d(2, 2) on (1,C,H,W) (reference unet.py:42)."""
 
@@ -1582,6 +1613,12 @@ def masked_loss(out, img, mask, kind="mae"):
 
 def masked_loss_holdout(out, img, mask, sel, kind="mae"):
     return MaskedLossHoldoutFn.apply(out, img, mask, sel, 1 if kind == "mse" else 0)
+
+
+def model_reg(m, axes=()):
+    """--model_reg: (1/N) sum |m| (axes empty) or (1/N) sum over `axes` (dims >= 2 of m = (1, C, n0, n1[, n2])) of |forward difference|,
+    N = m.numel(), as an fp32 scalar with its gradient (ModelRegFn).  m: fp32, contiguous, on the GPU."""
+    return ModelRegFn.apply(m, tuple(axes))
 
 
 def ema_loss(out, avg, img, mask, sel, beta, step_lr, active=None, kind="mae"):

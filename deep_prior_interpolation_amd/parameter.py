@@ -6,6 +6,7 @@ parameter.py:4-130), table-driven.  Differences, both fixing upstream crashes (S
 from argparse import ArgumentParser, Namespace
 
 _ACT = ["LeakyReLU", "ReLU", "ELU", "Tanh", "Sigmoid"]
+MODEL_REG_KINDS = ("l1", "tv_t", "tv_x", "tv")
 
 # (flags, kwargs)
 _FLAGS = [
@@ -160,6 +161,14 @@ _FLAGS = [
     (("--moveout_interp",), dict(type=str, required=False, default="linear", choices=["linear", "cubic"],
                                 help="ours: how --moveout reads the model along t: linear = 2 taps, cubic = 4 taps (Keys, a = -1/2); needs "
                                      "--moveout")),
+    # penalty on the tensor the network writes (ours: the reference has no prior on the model but the architecture)
+    (("--model_reg",), dict(type=str, required=False, choices=list(MODEL_REG_KINDS),
+                           help="ours: penalty on the tensor the network itself writes, before --avo_theta / --wavelet / --moveout map it to "
+                                "the data (absent = off): l1 = mean |m| (sparse reflectivity), tv_t = mean |difference along t| (blocky "
+                                "impedance), tv_x = the same along every other non-channel axis (flat gathers), tv = along all of them "
+                                "(anisotropic total variation).  Every kind divides by the element count; needs --model_reg_weight")),
+    (("--model_reg_weight",), dict(type=float, required=False, default=0.0,
+                                  help="ours: weight W > 0 of --model_reg: total = misfit (+ aa_weight * R_aa) + W * R(m)")),
     # POCS regulariser (main_pocs.py)
     (("--pocs_alpha",), dict(type=float, required=False, default=0.1, help="POCS data weighting.")),
     (("--pocs_thresh",), dict(type=float, required=False, default=5.0, help="POCS thresholding percentage")),
@@ -201,6 +210,7 @@ def postprocess(args: Namespace) -> Namespace:
     check_avo(args)
     check_wavelet(args)
     check_moveout(args)
+    check_model_reg(args)
     return args
 
 
@@ -276,6 +286,40 @@ def check_moveout(args: Namespace):
         raise ValueError("--moveout does not combine with --data_forgetting_factor %d: it adds data-domain traces to the input of a "
                          "network that writes the model domain" % args.data_forgetting_factor)
     return name, interp
+
+
+def model_reg_axes(kind, datadim, slice):
+    """The dims of the device tensor (1, C, n0, n1[, n2]) that --model_reg `kind` differences: () for l1.  Time is dim 2 for --datadim 2d,
+    3d and 2.5d with --slice tx | ty (the rule of check_wavelet); the xy slabs are (X, Y, T-as-channels): both dims lateral, no time axis."""
+    if kind not in MODEL_REG_KINDS:
+        raise ValueError("--model_reg must be one of %s, got %r" % (", ".join(MODEL_REG_KINDS), kind))
+    dims = (2, 3, 4) if datadim == "3d" else (2, 3)
+    time = () if (datadim == "2.5d" and slice == "xy") else (2,)
+    if kind == "l1":
+        return ()
+    if kind == "tv_t":
+        if not time:
+            raise ValueError("--model_reg tv_t needs the time axis as dim 2 of the patch: --datadim 2d, 3d, or 2.5d with --slice tx or ty; "
+                             "--slice %s stacks t into the channels" % slice)
+        return time
+    return dims if kind == "tv" else tuple(d for d in dims if d not in time)
+
+
+def check_model_reg(args: Namespace):
+    """--model_reg and what it needs; returns None when it is off (also for a Namespace without the keys, as those of older args.txt
+    files), else (kind, weight, dims of the device tensor that are differenced)."""
+    kind = getattr(args, "model_reg", None)
+    weight = getattr(args, "model_reg_weight", None)
+    weight = 0.0 if weight is None else float(weight)
+    if kind is None:
+        if weight != 0.0:
+            raise ValueError("--model_reg_weight %g needs --model_reg: without a kind nothing is penalised and the flag would silently do "
+                             "nothing" % weight)
+        return None
+    axes = model_reg_axes(kind, args.datadim, args.slice)
+    if not (weight > 0.0 and weight < float("inf")):
+        raise ValueError("--model_reg %s needs --model_reg_weight W with a finite W > 0, got %r" % (kind, weight))
+    return kind, weight, axes
 
 
 def check_avo(args: Namespace):

@@ -8,7 +8,8 @@ import torch
 from .generic import ten_digit
 
 __all__ = ["snr", "pcorr", "History", "HistoryReg", "HistoryHoldout", "HistoryRegHoldout", "HistoryEma", "HistoryRegEma",
-           "HistoryHoldoutEma", "HistoryRegHoldoutEma", "history_class", "select_latest_min"]
+           "HistoryHoldoutEma", "HistoryRegHoldoutEma", "HistoryModelReg", "HistoryModelRegHoldout", "HistoryModelRegEma",
+           "HistoryModelRegHoldoutEma", "history_class", "select_latest_min"]
 
 
 def _lib(output, target):
@@ -207,8 +208,69 @@ class HistoryRegHoldoutEma(_EmaColumns, HistoryRegHoldout):
         self._init_ema(True)
 
 
-def history_class(reg=False, holdout=False, ema=False):
-    """The History class of a run: reg = a regulariser splits the loss, holdout = --holdout > 0, ema = --out_ema > 0."""
+class _ModelRegColumns:
+    """model_reg column of a run with --model_reg: the unweighted penalty R(m) on the tensor the network wrote.  Such a history is of
+    the HistoryReg family: loss is the total, df the misfit, reg the unweighted anti-aliasing term (0.0 without --aa_weight)."""
+    _mmsg = ", MREG = %.2e"
+
+    def _init_model_reg(self):
+        self.model_reg = []
+
+    def append_model_reg(self, value):
+        self.model_reg.append(value)
+
+    def log_message(self, idx):
+        return super().log_message(idx) + self._mmsg % self.model_reg[idx]
+
+    def __len__(self):
+        n = super().__len__()
+        assert len(self.model_reg) == n
+        return n
+
+    def __str__(self):
+        return super().__str__() + "\nMREG : %s" % (self.model_reg,)
+
+    __repr__ = __str__
+
+
+class HistoryModelReg(_ModelRegColumns, HistoryReg):
+    """HistoryReg of a run with --model_reg."""
+
+    def __init__(self, epochs):
+        HistoryReg.__init__(self, epochs)
+        self._init_model_reg()
+
+
+class HistoryModelRegHoldout(_ModelRegColumns, HistoryRegHoldout):
+    """HistoryReg of a run with --model_reg and --holdout: val_loss stays the pure data misfit."""
+
+    def __init__(self, epochs):
+        HistoryRegHoldout.__init__(self, epochs)
+        self._init_model_reg()
+
+
+class HistoryModelRegEma(_ModelRegColumns, HistoryRegEma):
+    """HistoryReg of a run with --model_reg and --out_ema."""
+
+    def __init__(self, epochs):
+        HistoryRegEma.__init__(self, epochs)
+        self._init_model_reg()
+
+
+class HistoryModelRegHoldoutEma(_ModelRegColumns, HistoryRegHoldoutEma):
+    """HistoryReg of a run with --model_reg, --holdout and --out_ema."""
+
+    def __init__(self, epochs):
+        HistoryRegHoldoutEma.__init__(self, epochs)
+        self._init_model_reg()
+
+
+def history_class(reg=False, holdout=False, ema=False, model_reg=False):
+    """The History class of a run: reg = a regulariser splits the loss, holdout = --holdout > 0, ema = --out_ema > 0, model_reg =
+    --model_reg (always of the HistoryReg family, with the model_reg column)."""
+    if model_reg:
+        return {(False, False): HistoryModelReg, (True, False): HistoryModelRegHoldout,
+                (False, True): HistoryModelRegEma, (True, True): HistoryModelRegHoldoutEma}[(bool(holdout), bool(ema))]
     return {(False, False, False): History, (True, False, False): HistoryReg,
             (False, True, False): HistoryHoldout, (True, True, False): HistoryRegHoldout,
             (False, False, True): HistoryEma, (True, False, True): HistoryRegEma,

@@ -659,6 +659,24 @@ int dpi_wavelet_adj(const float* d, const float* taps, int K, int diff, int C, i
 int dpi_moveout_fwd(const float* m, const float* tau, int interp, int C, int T, size_t S, float* d, void* stream);
 int dpi_moveout_adj(const float* d, const float* tau, const int* range, int interp, int C, int T, size_t S, float* m, void* stream);
 
+/* ---------------------------------------------------------------- Penalty on the model (--model_reg) --
+ * Ours (the reference has no prior on what the network writes): plain L1 or anisotropic total variation of m = [C][n0][n1][n2] fp32,
+ * contiguous, N = C n0 n1 n2, value and gradient in one launch.  Bit k of `axes` asks for the differences along n_k; channels are
+ * never differenced; axes = 0 is plain L1.
+ *     res[0]  = (1/N) sum_{a in axes} sum_i |m[i + e_a] - m[i]| over the pairs inside      (axes = 0: (1/N) sum_i |m[i]|)
+ *     grad[i] = (float)k[i] / (float)N with the INTEGER k[i] = sum_a ( sgn(m[i] - m[i - e_a]) [i_a >= 1] - sgn(m[i + e_a] - m[i])
+ *               [i_a < n_a - 1] ), axes = 0: sgn(m[i]); sgn from comparisons, sgn(0) = 0: one rounding, the same bits as any restatement.
+ * Every |a - b| is formed in fp32 and summed in double: per workgroup into ws (dpi_model_reg_ws_doubles(N) doubles), then by a second
+ * launch of one wave in a fixed order (the scheme of dpi_masked_loss).  No atomics, one thread per output: repeated launches give the
+ * same bits of grad and res.  An axis of extent 1 contributes nothing.  Any 4-byte aligned tensors: 16-byte accesses along n2 when
+ * n2 % 4 == 0 and m and grad both start on 16 bytes, four 4-byte accesses per lane otherwise, with the same bits either way.  A 4-D
+ * device tensor (1, C, a, b) is passed as n0 = 1, n1 = a, n2 = b with the bits shifted to match.  Null or aliased pointers, C or an
+ * extent < 1, axes outside [0, 7] and a tensor of 2^32 or more groups of four along n2 return an error before any launch.  ABI version
+ * stays: a stale library fails on the unresolved symbols. */
+size_t dpi_model_reg_ws_doubles(size_t n);
+int dpi_model_reg(const float* m, int C, size_t n0, size_t n1, size_t n2, int axes /* bit k: differences along n_k; 0 = plain L1 */,
+                  float* grad, double* ws, double* res /* [1]: R */, void* stream);
+
 /* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
  * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
  * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]
