@@ -145,6 +145,10 @@ SIGNATURES = {
     # along n_k, 0 = plain L1, res = double[1].  ABI_VERSION stays: a stale library fails on the unresolved symbols
     "dpi_model_reg_ws_doubles": (_Z, [_Z]),
     "dpi_model_reg": (_I, [_P, _I, _Z, _Z, _Z, _I, _P, _P, _P, _P]),
+    # --moveout_offset (ours): (d, mask, offset, vel, NV, stretch, T, S, n_groups, group_stride, n_traces, trace_stride, num, den, cnt, stream);
+    # d / mask = [T][S] fp32, offset = [S] / vel = [NV] float64, num / den = [G][NV][T] float64, cnt the same as int32.  ABI_VERSION stays: a
+    # stale library fails on the unresolved symbol
+    "dpi_semblance_sums": (_I, [_P, _P, _P, _P, _I, C.c_double, _I, _Z, _I, _Z, _I, _Z, _P, _P, _P, _P]),
     # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

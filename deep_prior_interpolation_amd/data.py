@@ -58,7 +58,8 @@ _transpose_patches_25d = transpose_patches_25d
 def extract_patches(args) -> List[dict]:
     """List of {'image': patch*gain, 'mask': binary patch, 'name': zero-padded index} (data.py:44-84).  With --trace_offsets (ours) each
     dict gains 'offsets', the (X, Y, 2) window of the file (2-D: (X, 1, 2) with dy = 0) cut at the origin of its image and mask windows.
-    With --moveout (ours) each dict gains 'moveout': all of t and the patch's x / y window of the table."""
+    With --moveout or --moveout_offset (ours) each dict gains 'moveout': all of t and the patch's x / y window of the table; with
+    --moveout_offset also 'moveout_velocity', the picked law (T,) of the volume or the laws (T, G_window) of the patch's gathers."""
     original = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     corrupted = np.load(os.path.join(args.imgdir, args.maskname), allow_pickle=True)
     assert original.shape == corrupted.shape, "Original and Corrupted data must have the same dimension"
@@ -67,7 +68,10 @@ def extract_patches(args) -> List[dict]:
         corrupted = u.bool2bin(corrupted)
     off = load_trace_offsets(args, original.shape)       # --trace_offsets: refused here, before any window is cut, where it cannot be served
     pe = patch_extractor_for(original.shape, args.patch_shape, args.patch_stride, args.datadim, args.imgchannel)
-    mov = load_moveout(args, original.shape, pe)         # --moveout: refused here as well, a time-tiled patch included
+    # --moveout / --moveout_offset: refused here as well, a time-tiled patch included; the scan reads the known traces of the volume
+    scan = {}
+    scanned = getattr(args, "moveout_offset", None) is not None
+    mov = load_moveout(args, original.shape, pe, volume=original * args.gain if scanned else None, mask=corrupted, scan=scan)
     if args.datadim == "2.5d" or (args.datadim == "2d" and pe.ndim == 3):
         final_shape = (-1,) + pe.dim              # last axis = channels
     else:
@@ -84,6 +88,7 @@ def extract_patches(args) -> List[dict]:
         msk = transpose_patches_25d(msk, args.slice)
     offs = _trace_offset_windows(args, off, original.shape, pe)
     movs = _moveout_windows(args, mov, original.shape, pe)
+    laws = _velocity_windows(args, scan, original.shape, pe)
     width = u.ten_digit(img.shape[0])
     out = []
     for p in range(img.shape[0]):
@@ -95,6 +100,8 @@ def extract_patches(args) -> List[dict]:
             out[-1]["offsets"] = offs[p]
         if movs is not None:
             out[-1]["moveout"] = movs[p]
+        if laws is not None:
+            out[-1]["moveout_velocity"] = laws[p]
     return out
 
 
@@ -131,11 +138,19 @@ def load_trace_offsets(args, vol_shape):
     return off
 
 
-def load_moveout(args, vol_shape, pe=None):
+def load_moveout(args, vol_shape, pe=None, volume=None, mask=None, scan=None):
     """--moveout: the table of the file as fp32 in the volume's shape — (T, X, Y) for --datadim 3d, (T, X) for --datadim 2d —, checked once
     for the whole volume (operators.check_moveout_table); None when the flag is off.  A geometry the flag does not serve, a wrong shape,
     non-finite values, live values that decrease along t and, with the patch extractor given, a patch that does not span the time axis
-    raise ValueError."""
+    raise ValueError.
+    --moveout_offset: the same table, built by operators.scan_table from the known traces of `volume` (gained, the volume's shape) under
+    `mask` (non-zero = known) and the offsets of the file, on the current device; `scan`, a dict, receives what scan_table returned.  The
+    kernel sums in a fixed order and the picker is float64 numpy in a fixed order: every rank of parallel.py computes the same table
+    from the same files, so nothing is communicated."""
+    from .parameter import check_moveout_scan
+    flags = check_moveout_scan(args)
+    if flags is not None:
+        return _scan_moveout(args, flags, vol_shape, pe, volume, mask, scan)
     name = getattr(args, "moveout", None)
     if name is None:
         return None
@@ -154,6 +169,47 @@ def load_moveout(args, vol_shape, pe=None):
         return check_moveout_table(tab, what="the table")[0]
     except ValueError as e:
         raise ValueError("--moveout %s: %s" % (name, e)) from e
+
+
+def _scan_moveout(args, flags, vol_shape, pe, volume, mask, scan):
+    """--moveout_offset: the offsets of the file, checked, -> the scanned table as load_moveout returns a table read from a file."""
+    name = flags["file"]
+    if args.datadim not in ("2d", "3d") or len(vol_shape) != (2 if args.datadim == "2d" else 3):
+        raise ValueError("--moveout_offset needs --datadim 3d on a (T, X, Y) volume or --datadim 2d on a (T, X) section, got --datadim %s "
+                         "on a volume of shape %s" % (args.datadim, tuple(vol_shape)))
+    if pe is not None and int(pe.dim[0]) != int(vol_shape[0]):
+        raise ValueError("--moveout_offset needs patches that span the whole time axis (%d samples), got %d along t from --patch_shape: "
+                         "the table can point anywhere along a trace, so a window in t cannot be served" % (vol_shape[0], pe.dim[0]))
+    off = np.load(os.path.join(args.imgdir, name), allow_pickle=False)
+    want = (tuple(vol_shape[1:]),) if len(vol_shape) == 3 else ((vol_shape[1],), (vol_shape[1], 1))
+    if off.shape not in want or off.dtype.kind not in "fiu":
+        raise ValueError("--moveout_offset %s holds %s %s for a volume of shape %s: expected real numbers of shape %s"
+                         % (name, off.dtype, tuple(off.shape), tuple(vol_shape), " or ".join(str(w) for w in want)))
+    off = off.astype(np.float64).reshape(vol_shape[1:])
+    if not np.all(np.isfinite(off)):
+        raise ValueError("--moveout_offset %s holds non-finite values" % name)
+    if volume is None or mask is None:
+        raise ValueError("--moveout_offset %s: the scan needs the volume and its mask (data.extract_patches passes them)" % name)
+    from .operators.moveout import check_moveout_table
+    from .operators.velocity import scan_table
+    known = np.asarray(mask) != 0
+    try:
+        res = scan_table(np.where(known, np.asarray(volume), 0.0), known, off, flags["vmin"], flags["vmax"], flags["nv"], gather=flags["gather"],
+                         window=flags["window"], min_fold=flags["min_fold"], max_step=flags["max_step"], stretch_mute=flags["stretch_mute"])
+    except ValueError as e:
+        raise ValueError("--moveout_offset %s: %s" % (name, e)) from e
+    if scan is not None:
+        scan.update(res, gather=flags["gather"])
+    return check_moveout_table(res["table"], what="the table")[0]
+
+
+def _velocity_windows(args, scan, vol_shape, pe):
+    """The picked laws that belong to each image window (--moveout_offset), in the order of the image windows; None without a scan."""
+    if not scan:
+        return None
+    from .operators.velocity import velocity_windows
+    origins = u.window_origins(vol_shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
+    return velocity_windows(scan["velocity"], scan["gather"], origins, pe.dim)
 
 
 def _moveout_windows(args, tab, vol_shape, pe):

@@ -58,6 +58,7 @@ class ForwardModel:
         self._data = [s for s in self.stages if s.domain == "data"]
         self.pre = self.best = self._buffer = None               # the tracked stage's input: this iteration / selected / captured copy
         self.trace_offsets = self.live = None                    # per patch: (X, Y, 2) as used, i.e. zero at unknown traces / L's live map
+        self.velocity = None                                     # per patch, --moveout_offset: (T,) or (T, G_window), the picked law(s)
 
     def stage(self, name):
         """The stage `name`, or None when there is none (its flag is off)."""
@@ -80,6 +81,7 @@ class ForwardModel:
         counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped)."""
         self._load_sampling(data.get("offsets"), shape, mask, name)
         self._load_moveout(data.get("moveout"), shape, name)
+        self.velocity = data.get("moveout_velocity")             # --moveout_offset: the picked law(s) behind the patch's table
         avo = self.stage("avo")
         if self.flags["avo"] is not None and (avo.op is None or avo.op.nt0 != int(shape[0])):       # kept while T stays the same
             from .operators import AVOLinearModelling
@@ -209,6 +211,10 @@ class ForwardModel:
             # the fp32 table window as used and the flattened section behind `output`
             op = self.stage("moveout").op
             run.update(moveout=None if op is None else op.table.copy(), moveout_interp=f["moveout"][1], moveout_model=self.model("moveout"))
+            if f["moveout"][0].startswith("scan:"):
+                # --moveout_offset: the picked law(s) the table was built from and the trial velocities [VMIN, VMAX, NV] of the scan
+                run.update(moveout_velocity=None if self.velocity is None else np.array(self.velocity, dtype=np.float64),
+                           moveout_vscan=[float(v) for v in self.args.moveout_vscan])
         if f["sampling"] is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
             run["trace_interp"] = self.trace_interp

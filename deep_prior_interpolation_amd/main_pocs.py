@@ -46,6 +46,9 @@ class Interpolator(_Base):
         if getattr(args, "moveout", None) is not None:
             raise ValueError("main_pocs does not support --moveout: the POCS projection thresholds and re-inserts traces in the data "
                              "domain, the network writes the flattened one; run main.py")
+        if getattr(args, "moveout_offset", None) is not None:
+            raise ValueError("main_pocs does not support --moveout_offset: the scanned table feeds the operator of --moveout, which the "
+                             "POCS projection cannot sit behind; run main.py")
         if getattr(args, "model_reg", None) is not None:
             raise ValueError("main_pocs does not support --model_reg: its regularisation hook and its history hold the POCS term; run "
                              "main.py")

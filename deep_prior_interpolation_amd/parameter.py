@@ -160,7 +160,29 @@ _FLAGS = [
                               "whole time axis; the section is saved as moveout_model")),
     (("--moveout_interp",), dict(type=str, required=False, default="linear", choices=["linear", "cubic"],
                                 help="ours: how --moveout reads the model along t: linear = 2 taps, cubic = 4 taps (Keys, a = -1/2); needs "
-                                     "--moveout")),
+                                     "--moveout or --moveout_offset")),
+    # the moveout table from a semblance velocity scan (ours: the reference estimates no velocity)
+    (("--moveout_offset",), dict(type=str, required=False,
+                                help="ours: a .npy in --imgdir with the source-receiver offset of every trace in cells (absent = off): "
+                                     "(X, Y) for --datadim 3d, (X,) or (X, 1) for --datadim 2d.  The table of --moveout is then built from "
+                                     "the data: a semblance scan over the known traces (--moveout_vscan), a picked law v(tau) per gather "
+                                     "and operators.nmo_table on it; everything else is the path of --moveout, which it replaces")),
+    (("--moveout_vscan",), dict(type=float, nargs=3, required=False, metavar=("VMIN", "VMAX", "NV"),
+                               help="ours: the trial velocities of --moveout_offset, np.linspace(VMIN, VMAX, NV) in cells per sample, "
+                                    "0 < VMIN <= VMAX, NV >= 1; required with --moveout_offset")),
+    (("--moveout_gather",), dict(type=str, required=False, choices=["volume", "x", "y"],
+                                help="ours: what shares one law v(tau) under --moveout_offset: volume = all traces (the default), x = the "
+                                     "Y traces of every x index, y = the X traces of every y index; --datadim 2d takes volume only")),
+    (("--moveout_stretch",), dict(type=float, required=False,
+                                 help="ours: the stretch mute S > 0 of --moveout_offset (absent = none): the scan skips samples with "
+                                      "t > S * tau and the table mutes samples stretched by more than S")),
+    (("--moveout_window",), dict(type=int, required=False,
+                                help="ours: half width in rows of the semblance window of --moveout_offset (default 2)")),
+    (("--moveout_min_fold",), dict(type=int, required=False,
+                                  help="ours: fewest live traces a row of the scan of --moveout_offset counts with (default 4)")),
+    (("--moveout_max_step",), dict(type=int, required=False,
+                                  help="ours: most velocity steps the picked law of --moveout_offset changes by from one row to the "
+                                       "next (default 1)")),
     # penalty on the tensor the network writes (ours: the reference has no prior on the model but the architecture)
     (("--model_reg",), dict(type=str, required=False, choices=list(MODEL_REG_KINDS),
                            help="ours: penalty on the tensor the network itself writes, before --avo_theta / --wavelet / --moveout map it to "
@@ -260,11 +282,61 @@ def check_wavelet(args: Namespace):
     return name, kind
 
 
+_VSCAN_ONLY = ("moveout_vscan", "moveout_gather", "moveout_stretch", "moveout_window", "moveout_min_fold", "moveout_max_step")
+
+
+def check_moveout_scan(args: Namespace):
+    """--moveout_offset and its own flags; returns None when it is off (also for a Namespace without the keys), else the dict of what
+    operators.scan_table takes: file, vmin, vmax, nv, gather, stretch_mute, window, min_fold, max_step.  The flags of the scan are refused
+    without --moveout_offset, where they would silently do nothing."""
+    name = getattr(args, "moveout_offset", None)
+    if name is None:
+        given = [k for k in _VSCAN_ONLY if getattr(args, k, None) is not None]
+        if given:
+            raise ValueError("--%s needs --moveout_offset: without offsets nothing is scanned and the flag would silently do nothing"
+                             % ", --".join(given))
+        return None
+    if getattr(args, "moveout", None) is not None:
+        raise ValueError("--moveout_offset does not combine with --moveout %s: the table is either read or scanned" % (args.moveout,))
+    vscan = getattr(args, "moveout_vscan", None)
+    if vscan is None:
+        raise ValueError("--moveout_offset needs --moveout_vscan VMIN VMAX NV: the trial velocities of the scan, in cells per sample")
+    if len(vscan) != 3:
+        raise ValueError("--moveout_vscan takes VMIN VMAX NV, got %r" % (vscan,))
+    vmin, vmax, nv = (float(v) for v in vscan)
+    if not (vmin > 0.0 and vmax >= vmin and vmax < float("inf")):
+        raise ValueError("--moveout_vscan needs 0 < VMIN <= VMAX (cells per sample), got %g, %g" % (vmin, vmax))
+    if not (nv >= 1.0 and nv == int(nv)):
+        raise ValueError("--moveout_vscan needs a whole number NV >= 1 of velocities, got %r" % (vscan[2],))
+    gather = getattr(args, "moveout_gather", None) or "volume"
+    if gather not in ("volume", "x", "y"):
+        raise ValueError("--moveout_gather must be volume, x or y, got %r" % (gather,))
+    if args.datadim == "2d" and gather != "volume":
+        raise ValueError("--moveout_gather %s needs --datadim 3d: a (T, X) section is one gather (volume)" % gather)
+    stretch = getattr(args, "moveout_stretch", None)
+    if stretch is not None and not (float(stretch) > 0.0 and float(stretch) < float("inf")):
+        raise ValueError("--moveout_stretch must be a finite value > 0, got %r" % (stretch,))
+    out = {"file": name, "vmin": vmin, "vmax": vmax, "nv": int(nv), "gather": gather,
+           "stretch_mute": None if stretch is None else float(stretch)}
+    for key, default, least in (("window", 2, 0), ("min_fold", 4, 0), ("max_step", 1, 0)):
+        v = getattr(args, "moveout_" + key, None)
+        v = default if v is None else v
+        if int(v) != v or v < least:
+            raise ValueError("--moveout_%s must be a whole number >= %d, got %r" % (key, least, v))
+        out[key] = int(v)
+    return out
+
+
 def check_moveout(args: Namespace):
-    """--moveout and what it cannot be combined with; returns None when it is off (also for a Namespace without the keys, as those of
-    older args.txt files), else (file name, interp).  The file itself is read and checked by data.extract_patches, which also refuses a
-    patch that does not span the time axis."""
+    """--moveout / --moveout_offset and what they cannot be combined with; returns None when both are off (also for a Namespace without
+    the keys, as those of older args.txt files), else (file name, interp) for --moveout and ("scan:" + file name, interp) for
+    --moveout_offset (check_moveout_scan has its flags).  The file itself is read and checked by data.extract_patches, which also refuses
+    a patch that does not span the time axis."""
+    scan = check_moveout_scan(args)
     name = getattr(args, "moveout", None)
+    flag = "--moveout"
+    if scan is not None:
+        name, flag = "scan:" + scan["file"], "--moveout_offset"
     interp = getattr(args, "moveout_interp", None) or "linear"
     if interp not in ("linear", "cubic"):
         raise ValueError("--moveout_interp must be linear or cubic, got %r" % (interp,))
@@ -274,17 +346,17 @@ def check_moveout(args: Namespace):
                              "nothing" % interp)
         return None
     if args.datadim not in ("2d", "3d"):
-        raise ValueError("--moveout needs --datadim 2d or 3d, got --datadim %s: a 2.5-D slab is not served" % args.datadim)
+        raise ValueError("%s needs --datadim 2d or 3d, got --datadim %s: a 2.5-D slab is not served" % (flag, args.datadim))
     if getattr(args, "avo_theta", None) is not None:
-        raise ValueError("--moveout does not combine with --avo_theta, which needs --datadim 2.5d")
+        raise ValueError("%s does not combine with --avo_theta, which needs --datadim 2.5d" % flag)
     if getattr(args, "wavelet", None) is not None:
-        raise ValueError("--moveout does not combine with --wavelet: which of the two operators comes first is not decided yet")
+        raise ValueError("%s does not combine with --wavelet: which of the two operators comes first is not decided yet" % flag)
     if getattr(args, "net", "multiunet") == "part":
-        raise ValueError("--moveout does not combine with --net part: its hole map would live on the model's time axis, the mask on the "
-                         "data's")
+        raise ValueError("%s does not combine with --net part: its hole map would live on the model's time axis, the mask on the "
+                         "data's" % flag)
     if (getattr(args, "data_forgetting_factor", 0) or 0) > 0:
-        raise ValueError("--moveout does not combine with --data_forgetting_factor %d: it adds data-domain traces to the input of a "
-                         "network that writes the model domain" % args.data_forgetting_factor)
+        raise ValueError("%s does not combine with --data_forgetting_factor %d: it adds data-domain traces to the input of a "
+                         "network that writes the model domain" % (flag, args.data_forgetting_factor))
     return name, interp
 
 
@@ -408,6 +480,9 @@ _OURS_MUST_MATCH = (
     ("trace_offsets", None, _same), ("trace_interp", "linear", _same),
     ("wavelet", None, _same), ("wavelet_model", "reflectivity", _same),
     ("moveout", None, _same), ("moveout_interp", "linear", _same),
+    # the scanned table: what decides it (window, fold and step only tune the pick; the table itself is saved with the run)
+    ("moveout_offset", None, _same), ("moveout_vscan", None, lambda v: None if v is None else [float(x) for x in v]),
+    ("moveout_gather", "volume", _same), ("moveout_stretch", None, lambda v: None if v is None else float(v)),
 )
 
 

@@ -677,6 +677,28 @@ size_t dpi_model_reg_ws_doubles(size_t n);
 int dpi_model_reg(const float* m, int C, size_t n0, size_t n1, size_t n2, int axes /* bit k: differences along n_k; 0 = plain L1 */,
                   float* grad, double* ws, double* res /* [1]: R */, void* stream);
 
+/* ---------------------------------------------------------------- Semblance velocity scan (--moveout_offset) --
+ * Ours (the reference estimates no velocity): the three sums behind a semblance panel, over the known traces of a gather along the
+ * hyperbola of every trial velocity.  d, mask: [T][S] fp32 on the device (mask: non-zero = known), any 4-byte aligned address;
+ * offset: [S] float64 in cells; vel: [NV] float64 in cells per sample, > 0; stretch: float64, <= 0 = no stretch mute.  Trace k of
+ * gather g is column g * group_stride + k * trace_stride, g < n_groups, k < n_traces.  On a (T, X, Y) volume, S = X Y:
+ *     the whole cube one gather:               (n_groups, group_stride, n_traces, trace_stride) = (1, 0, S, 1)
+ *     every y index a gather of its X traces:  (Y, 1, X, Y)
+ *     every x index a gather of its Y traces:  (X, Y, Y, 1)
+ * For gather g, velocity v, zero-offset row tau and trace s of that gather, everything in float64:
+ *     t = sqrt(tau^2 + (offset[s] / vel[v])^2)
+ *     live iff t <= T - 1 and (stretch <= 0 or t <= stretch * tau) and both tap rows i, i + 1 of column s are known
+ *     i = min(floor(t), T - 2), f = t - i, a = (1 - f) d[i][s] + f d[i + 1][s]       (T = 1: i = 0, row 0 alone, a = d[0][s])
+ *     num[g][v][tau] = sum a, den[g][v][tau] = sum a^2, cnt[g][v][tau] = the number of live traces        (float64, float64, int32)
+ * A lane adds its traces in ascending order, a wave is folded by shuffles, the waves that share a row are added in ascending order through
+ * LDS: no atomics, repeated launches give the same bits.  A sample that is not live reads nothing and a live one has 0 <= i <= T - 2: no
+ * offset, velocity or mask (NaN included: not live) sends a load out of bounds.  The inputs are read only and may share memory.  A null
+ * pointer, an output that shares memory with an input or another output, T, S, NV, n_groups or n_traces < 1, a geometry whose last
+ * column (n_groups - 1) group_stride + (n_traces - 1) trace_stride is not below S and T > 2^24 return an error before any launch.  ABI
+ * version stays: a stale library fails on the unresolved symbol. */
+int dpi_semblance_sums(const float* d, const float* mask, const double* offset, const double* vel, int NV, double stretch, int T, size_t S,
+                       int n_groups, size_t group_stride, int n_traces, size_t trace_stride, double* num, double* den, int* cnt, void* stream);
+
 /* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
  * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
  * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]
