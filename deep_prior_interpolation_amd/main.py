@@ -1,5 +1,6 @@
 """Per-patch deep-prior optimiser — drop-in for reference main.py (Interpolator life-cycle
-load_data -> build_model -> build_input -> optimize -> save_result -> clean, and the `main()` CLI).
+load_data -> build_model -> build_input -> optimize -> save_result -> clean, and the `main()` CLI).  The life-cycle of one patch is
+written once, in Interpolator.take_patch / prepare_patch / run_patch: every driver (run_cli here, parallel.py) goes through them.
 
 Everything inside the iteration runs on the GPU through libdpi_hip.so: input perturbation (Philox),
 network forward/backward (HIP convs / BN / up-sampling), fused masked loss + SNR/PCORR, fused Adam.
@@ -79,8 +80,50 @@ class Interpolator:
         self.noise_seed = int(seed)
         self._noise_step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._patches_seen = 0          # mixed into the Philox stream id of z: every patch gets its own z (main.py:62-64 draws a fresh one)
+        self.patch_index = self.patch_std = None                 # of the patch taken last (take_patch)
 
-    # ------------------------------------------------------------------------------------------
+    # ---- the life-cycle of one patch (reference main.py:274-295): the drivers call these, none spells the steps out ------------------
+    def take_patch(self, index, patch):
+        """Load patch `index` and decide whether there is anything to optimise.  A flat patch (std of the masked data 0: nothing
+        recorded in it) is its own result, out_best = img * mask at no cost.  Returns whether the patch is live."""
+        self.patch_index = int(index)
+        self.patch_std = self.load_data(patch)
+        live = not np.isclose(self.patch_std, 0.0, atol=1e-12)
+        if not live:
+            self.out_best, self.elapsed, self._out_best_dev = self.img * self.mask, 0.0, None
+        return live
+
+    def prepare_patch(self):
+        """Everything between take_patch() and the loop of a live patch: the seeds, the network (kept from the patch before with
+        --start_from_prev, read from --netdir when given), z and the regulariser.  Separate from take_patch() because the concurrent
+        drivers prepare one patch while the captured iterations of others replay."""
+        i, a = self.patch_index, self.args
+        self.begin_patch(i)
+        if self.net is None or not a.start_from_prev:
+            self.build_model(netpath=a.netdir[i]) if len(a.netdir) != 0 else self.build_model()
+        self.build_input()
+        self.build_regularizer()
+
+    def run_patch(self, index, patch, verbose=True):
+        """One patch from its data to out_best, sequentially.  verbose prints what the reference's loop prints.  Returns take_patch()'s
+        answer; save_result() and clean() are the driver's."""
+        live = self.take_patch(index, patch)
+        if verbose:
+            print("\nThe data shape is %s, the std of coarse data is %.2e" % (str(patch["image"].shape), self.patch_std))
+            if not live:
+                print("skipping...")
+        if live:
+            self.prepare_patch()
+            self.optimize(verbose=verbose)
+        return live
+
+    def output_for_reassembly(self):
+        """The selected output as overlap-add takes it, without batch and channel axes: the device tensor of an optimised patch, the
+        host fp32 tensor of out_best for a flat one."""
+        if self._out_best_dev is None:
+            return torch.from_numpy(np.ascontiguousarray(self.out_best[..., 0], dtype=np.float32))
+        return self._out_best_dev.reshape(self._out_best_dev.shape[2:])
+
     def begin_patch(self, index, base_seed=0):
         """Seed everything patch `index` draws — initial weights (torch's CPU generator, consumed by init_weights), z and the
         per-iteration perturbation (Philox key) — from the patch index alone, so its result does not depend on which process,
@@ -641,12 +684,8 @@ class Interpolator:
         self.optimizer = self.make_optimizer()
         ops.set_weight_grad_overlap(big, in_graph=(mode == "graph" and big))
         start = time()
-        if mode == "graph" and self.noise_source() != "philox":
-            raise ValueError("--noise_source torch_cpu draws on the host every iteration: it cannot be captured (mode='eager')")
-        if mode == "graph" and self.model_reg is not None:
-            raise ValueError("--model_reg %s cannot be captured (mode='eager'): the captured iteration evaluates no regulariser, and the "
-                             "term must not be dropped silently" % self.model_reg[0])
         if mode == "graph":
+            self._check_capturable()
             self._optimize_graph(verbose, check_every)
         else:
             sched = DevicePlateau(self.optimizer, a.lr_factor, a.lr_thresh, a.lr_patience) if a.reduce_lr else None
@@ -690,11 +729,7 @@ class Interpolator:
         stream is synchronised before the capture and the capture is opened with CUDAGraph.capture_begin() directly (torch.cuda.graph()
         would synchronise the whole device, collect garbage and empty the allocator's cache first)."""
         a = self.args
-        if self.noise_source() != "philox":
-            raise ValueError("--noise_source torch_cpu draws on the host every iteration: it cannot be captured into a graph")
-        if self.model_reg is not None:
-            raise ValueError("--model_reg %s cannot be captured into a graph (mode='eager'): the captured iteration evaluates no "
-                             "regulariser, and the term must not be dropped silently" % self.model_reg[0])
+        self._check_capturable()
         L = _lib.load()
         dev = self.device
         if self.optimizer is None:
@@ -779,6 +814,15 @@ class Interpolator:
                     n, h, _ = self._g_rule.rows(self._g_state, self._g_hist)
                     print(self._g_rule.progress(n, h[-1]), "\r", end="")
         self.graph_finish()
+
+    def _check_capturable(self):
+        """The runs no captured iteration can serve, refused by optimize(mode='graph') and graph_prepare() alike (_eager_reasons() is
+        why mode='auto' never gets here with them)."""
+        if self.noise_source() != "philox":
+            raise ValueError("--noise_source torch_cpu draws on the host every iteration: it cannot be captured into a graph (mode='eager')")
+        if self.model_reg is not None:
+            raise ValueError("--model_reg %s cannot be captured into a graph (mode='eager'): the captured iteration evaluates no "
+                             "regulariser, and the term must not be dropped silently" % self.model_reg[0])
 
     def has_regularizer(self):
         return getattr(self, "_aa_op", None) is not None or self.model_reg is not None
@@ -904,7 +948,9 @@ def optimize_concurrently(Ts, check_every=64, prepare=None, timings=None):
         timings["prepare_s"] = timings.get("prepare_s", 0.0) + t_prep
 
 
-def main(argv=None):
+def run_cli(interpolator_cls, argv=None):
+    """The sequential command-line driver of main.py and main_pocs.py: every patch of the data set, one after the other, through
+    `interpolator_cls`."""
     args = parse_arguments(argv)
     u.set_gpu(args.gpu if args.gpu is not None else -1)
     u.set_seed(0)
@@ -914,24 +960,16 @@ def main(argv=None):
     u.write_args(os.path.join(outpath, "args.txt"), args)
     patches = extract_patches(args)
     print("Processing %d patches" % len(patches))
-    T = Interpolator(args, outpath)
+    T = interpolator_cls(args, outpath)
     for i, patch in enumerate(patches):
-        std = T.load_data(patch)
-        print("\nThe data shape is %s, the std of coarse data is %.2e" % (str(patch["image"].shape), std))
-        if np.isclose(std, 0.0, atol=1e-12):
-            print("skipping...")
-            T.out_best = T.img * T.mask
-            T.elapsed = 0.0
-        else:
-            T.begin_patch(i)
-            if T.net is None or not args.start_from_prev:
-                T.build_model(netpath=args.netdir[i]) if len(args.netdir) != 0 else T.build_model()
-            T.build_input()
-            T.build_regularizer()
-            T.optimize()
+        T.run_patch(i, patch)
         T.save_result()
         T.clean()
     print("Interpolation done! Saved to %s" % outpath)
+
+
+def main(argv=None):
+    run_cli(Interpolator, argv)
 
 
 if __name__ == "__main__":

@@ -18,9 +18,7 @@ import torch
 
 from . import ops
 from . import utils as u
-from .data import extract_patches
-from .main import Interpolator as _Base
-from .parameter import parse_arguments
+from .main import Interpolator as _Base, run_cli
 
 
 class Interpolator(_Base):
@@ -93,33 +91,7 @@ class Interpolator(_Base):
 
 
 def main(argv=None):
-    args = parse_arguments(argv)
-    u.set_gpu(args.gpu if args.gpu is not None else -1)
-    u.set_seed(0)
-    outpath = os.path.join("./results/", args.outdir if args.outdir is not None else u.random_code())
-    os.makedirs(outpath, exist_ok=True)
-    print("Saving to %s" % outpath)
-    u.write_args(os.path.join(outpath, "args.txt"), args)
-    patches = extract_patches(args)
-    print("Processing %d patches" % len(patches))
-    T = Interpolator(args, outpath)
-    for i, patch in enumerate(patches):
-        std = T.load_data(patch)
-        print("\nThe data shape is %s, the std of coarse data is %.2e" % (str(patch["image"].shape), std))
-        if np.isclose(std, 0.0, atol=1e-12):
-            print("skipping...")
-            T.out_best = T.img * T.mask
-            T.elapsed = 0.0
-        else:
-            T.begin_patch(i)
-            if T.net is None or not args.start_from_prev:
-                T.build_model(netpath=args.netdir[i]) if len(args.netdir) != 0 else T.build_model()
-            T.build_input()
-            T.build_regularizer()
-            T.optimize()
-        T.save_result()
-        T.clean()
-    print("Interpolation done! Saved to %s" % outpath)
+    run_cli(Interpolator, argv)
 
 
 if __name__ == "__main__":

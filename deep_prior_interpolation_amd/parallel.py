@@ -71,6 +71,28 @@ class PatchQueue:
         return [i for i in range(end - n, end) if i < self.num]
 
 
+def _window(origin, dim):
+    """The slices of the window of size `dim` at `origin`."""
+    return tuple(slice(int(o), int(o) + d) for o, d in zip(origin, dim))
+
+
+def _geometry(shape, dim, stride, host_cls=None):
+    """(shape, dim, stride) as tuples of ints; host_cls names the class to use instead when a device accumulator is asked for a volume
+    that is not 3-D."""
+    if host_cls is not None and len(shape) != 3:
+        raise NotImplementedError("device overlap-add handles 3-D volumes; use %s otherwise" % host_cls)
+    return tuple(int(v) for v in shape), tuple(int(v) for v in dim), tuple(int(v) for v in stride)
+
+
+def _device_patch(patch, acc, dim, what):
+    """`patch` (numpy or tensor) as a contiguous fp32 tensor of shape `dim` on the accumulator's device."""
+    p = patch if torch.is_tensor(patch) else torch.from_numpy(np.ascontiguousarray(patch, dtype=np.float32))
+    p = p.to(acc.device, torch.float32).contiguous()
+    if tuple(p.shape) != dim:
+        raise _lib.DpiError("%s shape %s != %s" % (what, tuple(p.shape), dim))
+    return p
+
+
 class HostOverlapAccumulator:
     """numpy overlap-add with the reference's arithmetic (float64 accumulate, utils/patch_extractor.py:395-426).
     Used for 2-D / 2.5-D data, by data.reconstruct_patches-style host flows and by the gloo (CPU) tests."""
@@ -80,8 +102,7 @@ class HostOverlapAccumulator:
         self.acc = torch.zeros(self.shape, dtype=torch.float64)
 
     def add(self, patch, origin):
-        sl = tuple(slice(int(o), int(o) + d) for o, d in zip(origin, self.dim))
-        self.acc[sl] += torch.as_tensor(np.asarray(patch), dtype=torch.float64)
+        self.acc[_window(origin, self.dim)] += torch.as_tensor(np.asarray(patch), dtype=torch.float64)
 
     def tensor(self):
         return self.acc
@@ -89,7 +110,7 @@ class HostOverlapAccumulator:
     def finalize(self, gain):
         hits = torch.zeros(self.shape, dtype=torch.float64)
         for org in u.window_origins(self.shape, self.dim, self.stride):
-            hits[tuple(slice(int(o), int(o) + d) for o, d in zip(org, self.dim))] += 1
+            hits[_window(org, self.dim)] += 1
         return (self.acc / hits / gain).numpy()
 
 
@@ -97,16 +118,11 @@ class DeviceOverlapAccumulator:
     """fp32 accumulator volume in HBM; dpi_overlap_add / dpi_overlap_normalize kernels (3-D volumes)."""
 
     def __init__(self, shape, dim, stride, device):
-        if len(shape) != 3:
-            raise NotImplementedError("device overlap-add handles 3-D volumes; use HostOverlapAccumulator otherwise")
-        self.shape, self.dim, self.stride = tuple(int(s) for s in shape), tuple(int(d) for d in dim), tuple(int(s) for s in stride)
+        self.shape, self.dim, self.stride = _geometry(shape, dim, stride, "HostOverlapAccumulator")
         self.acc = torch.zeros(self.shape, dtype=torch.float32, device=device)
 
     def add(self, patch, origin):
-        p = patch if torch.is_tensor(patch) else torch.from_numpy(np.ascontiguousarray(patch, dtype=np.float32))
-        p = p.to(self.acc.device, torch.float32).contiguous()
-        if tuple(p.shape) != self.dim:
-            raise _lib.DpiError("overlap_add: patch shape %s != %s" % (tuple(p.shape), self.dim))
+        p = _device_patch(patch, self.acc, self.dim, "overlap_add: patch")
         _lib.check(_lib.load().dpi_overlap_add(_lib.ptr(p), *self.dim, *[int(o) for o in origin], _lib.ptr(self.acc),
                                                *self.shape, _lib.stream()), "dpi_overlap_add")
 
@@ -125,13 +141,13 @@ class HostBlendAccumulator:
     left in `std_volume` (None without with_std)."""
 
     def __init__(self, shape, dim, stride, device="cpu", taper=False, with_std=False):
-        self.shape, self.dim, self.stride = tuple(int(v) for v in shape), tuple(int(v) for v in dim), tuple(int(v) for v in stride)
+        self.shape, self.dim, self.stride = _geometry(shape, dim, stride)
         self.taper, self.with_std = bool(taper), bool(with_std)
         self.acc = torch.zeros((3 if with_std else 2,) + self.shape, dtype=torch.float64)
         self.std_volume = None
 
     def add(self, patch, origin, std=None):
-        sl = tuple(slice(int(o), int(o) + d) for o, d in zip(origin, self.dim))
+        sl = _window(origin, self.dim)
         w = torch.from_numpy(u.patch_window(self.shape, self.dim, self.stride, origin, self.taper))
         self.acc[0][sl] += w
         self.acc[1][sl] += w * torch.as_tensor(np.asarray(patch), dtype=torch.float64)
@@ -155,9 +171,7 @@ class DeviceBlendAccumulator:
     host but a patch that is not on the device yet.  finalize() returns the mean volume and leaves the std volume in `std_volume`."""
 
     def __init__(self, shape, dim, stride, device, taper=False, with_std=False):
-        if len(shape) != 3:
-            raise NotImplementedError("device overlap-add handles 3-D volumes; use HostBlendAccumulator otherwise")
-        self.shape, self.dim, self.stride = tuple(int(s) for s in shape), tuple(int(d) for d in dim), tuple(int(s) for s in stride)
+        self.shape, self.dim, self.stride = _geometry(shape, dim, stride, "HostBlendAccumulator")
         self.taper, self.with_std = bool(taper), bool(with_std)
         self.K = 3 if self.with_std else 2
         self.acc = torch.zeros((self.K,) + self.shape, dtype=torch.float32, device=device)
@@ -166,16 +180,9 @@ class DeviceBlendAccumulator:
         self._zero_std = None
         self.std_volume = None
 
-    def _patch(self, patch, what):
-        p = patch if torch.is_tensor(patch) else torch.from_numpy(np.ascontiguousarray(patch, dtype=np.float32))
-        p = p.to(self.acc.device, torch.float32).contiguous()
-        if tuple(p.shape) != self.dim:
-            raise _lib.DpiError("overlap_add_weighted: %s shape %s != %s" % (what, tuple(p.shape), self.dim))
-        return p
-
     def add(self, patch, origin, std=None):
         """std=None with_std: the patch has no spread (skipped, or fewer than two samples) and contributes std 0."""
-        p = self._patch(patch, "patch")
+        p = _device_patch(patch, self.acc, self.dim, "overlap_add_weighted: patch")
         sd = None
         if self.with_std:
             if std is None:
@@ -183,7 +190,7 @@ class DeviceBlendAccumulator:
                     self._zero_std = torch.zeros(self.dim, dtype=torch.float32, device=self.acc.device)
                 sd = self._zero_std
             else:
-                sd = self._patch(std, "std")
+                sd = _device_patch(std, self.acc, self.dim, "overlap_add_weighted: std")
         elif std is not None:
             raise _lib.DpiError("overlap_add_weighted: a std patch needs an accumulator built with_std")
         origin = [int(o) for o in origin]
@@ -213,9 +220,21 @@ def _acc_add(acc, T, origin):
         sd = getattr(T, "_post_std_dev", None)
         if sd is not None and sd.is_cuda:
             sd.record_stream(torch.cuda.current_stream(sd.device))      # made on the patch's stream, read here, dropped by T.clean() right after
-        acc.add(T._best_for_acc, origin, std=None if sd is None else sd.reshape(sd.shape[2:]))
+        acc.add(T.output_for_reassembly(), origin, std=None if sd is None else sd.reshape(sd.shape[2:]))
     else:
-        acc.add(T._best_for_acc, origin)
+        acc.add(T.output_for_reassembly(), origin)
+
+
+def _finish_patch(T, mine, holdout_snrs, acc=None, origins=None, save=True):
+    """What every driver does with a patch whose out_best stands (Interpolator.run_patch, or take_patch / prepare_patch and a loop of the
+    driver's own): overlap-add into `acc` (the volume schedules), result file, held-out SNR for the summary, clean, note the index."""
+    if acc is not None:
+        _acc_add(acc, T, origins[T.patch_index])
+    if save:
+        T.save_result()
+    _record_holdout(T, holdout_snrs)
+    T.clean()
+    mine.append(T.patch_index)
 
 
 def gather_volume(acc):
@@ -324,18 +343,13 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
     Returns (indices processed, host seconds spent preparing while other slots were running)."""
     from time import perf_counter, sleep
     streams = [torch.cuda.Stream(device=device) for _ in Ts]
-    slot = [None] * len(Ts)            # per slot: {"i": patch index, "t0": start time, "entry": the replay thread's entry, "polled": replays at the last poll}
+    slot = [None] * len(Ts)            # per slot: {"t0": start time, "entry": the replay thread's entry, "polled": replays at the last poll}
     mine, t_prep = [], [0.0]
     main_stream = torch.cuda.current_stream(device)
     rep = _Replayer(device, int(os.environ.get("DPI_SLOT_DEPTH", "6")))
 
-    def done(T, i):
-        _acc_add(acc, T, origins[i])
-        if save:
-            T.save_result()
-        _record_holdout(T, holdout_snrs)
-        T.clean()
-        mine.append(i)
+    def done(T):
+        _finish_patch(T, mine, holdout_snrs, acc, origins, save)
 
     def start(k):
         """Claim and prepare the next graph-capable patch for slot k; False when the queue is empty."""
@@ -347,26 +361,19 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
                 return False
             i = got[0]
             t0 = perf_counter()
-            std = T.load_data(patches[i])
-            if np.isclose(std, 0.0, atol=1e-12):
-                T.out_best, T.elapsed = T.img * T.mask, 0.0
-                T._best_for_acc = torch.from_numpy(np.ascontiguousarray(T.out_best[..., 0], dtype=np.float32))
-                done(T, i)
+            if not T.take_patch(i, patches[i]):
+                done(T)
                 continue
-            T.begin_patch(i)
-            T.build_model(netpath=args.netdir[i]) if len(args.netdir) != 0 else T.build_model()
-            T.build_input()
-            T.build_regularizer()
+            T.prepare_patch()
             if not T.graph_capable():
                 T.optimize(verbose=False)
-                T._best_for_acc = T._out_best_dev.reshape(T._out_best_dev.shape[2:])
-                done(T, i)
+                done(T)
                 continue
             st.wait_stream(main_stream)                      # data / weights / z were produced on the caller's stream
             with torch.cuda.stream(st):
                 T.optimizer = None
                 g = T.graph_prepare(quiet_device=False)
-            slot[k] = {"i": i, "t0": t0, "entry": rep.add(g, st, args.epochs - 1), "polled": 0}
+            slot[k] = {"t0": t0, "entry": rep.add(g, st, args.epochs - 1), "polled": 0}
             t_prep[0] += perf_counter() - t0
             return True
 
@@ -377,8 +384,7 @@ def _optimise_rolling(args, patches, origins, acc, Ts, queue, save, device, chec
             T.graph_finish(quiet_device=False)               # waits for THIS slot's queued replays only
         main_stream.wait_stream(st)
         T.elapsed = perf_counter() - slot[k]["t0"]
-        T._best_for_acc = T._out_best_dev.reshape(T._out_best_dev.shape[2:])
-        done(T, slot[k]["i"])
+        done(T)
     primary = None
     try:
         for k in range(len(Ts)):
@@ -481,44 +487,23 @@ def optimise_volume(args, patches, origins, vol_shape, pe, device, outpath=None,
         t0 = perf_counter()
         t_solo = 0.0
         live = []
-        index_of = {}
-
-        def prepare(T):
-            i = index_of[id(T)]
-            T.begin_patch(i)
-            if T.net is None or not args.start_from_prev:
-                T.build_model(netpath=args.netdir[i]) if len(args.netdir) != 0 else T.build_model()
-            T.build_input()
-            T.build_regularizer()
         for T, i in zip(Ts, group):
-            std = T.load_data(patches[i])
-            if np.isclose(std, 0.0, atol=1e-12):
-                T.out_best, T.elapsed = T.img * T.mask, 0.0
-                T._best_for_acc = torch.from_numpy(np.ascontiguousarray(T.out_best[..., 0], dtype=np.float32))
+            if not T.take_patch(i, patches[i]):
                 continue
-            index_of[id(T)] = i
             if len(Ts) > 1 and T.graph_capable():
                 live.append(T)             # prepared inside optimize_concurrently, patch by patch, while the earlier ones already run
             else:
-                prepare(T)
+                T.prepare_patch()
                 torch.cuda.synchronize(device)
                 to = perf_counter()
                 T.optimize(verbose=False)
-                T._best_for_acc = T._out_best_dev.reshape(T._out_best_dev.shape[2:])
                 t_solo += perf_counter() - to          # a patch optimised on its own (>= 2^20 voxels, --save_every, ...): loop time, not set-up
         t1 = perf_counter()
         ct = {}
-        optimize_concurrently(live, prepare=prepare, timings=ct)
+        optimize_concurrently(live, prepare=lambda T: T.prepare_patch(), timings=ct)
         t_prep_live += ct.get("prepare_s", 0.0)
-        for T in live:
-            T._best_for_acc = T._out_best_dev.reshape(T._out_best_dev.shape[2:])
-        for T, i in zip(Ts, group):
-            _acc_add(acc, T, origins[i])
-            if save:
-                T.save_result()
-            _record_holdout(T, holdout_snrs)
-            T.clean()
-            mine.append(i)
+        for T in Ts[:len(group)]:
+            _finish_patch(T, mine, holdout_snrs, acc, origins, save)
         t_setup += t1 - t0 - t_solo
         t_loop += perf_counter() - t1 + t_solo
     if timings is not None:          # (bench.py) the collective ALONE, bracketed by device synchronisations, beside the rank's own seconds
@@ -583,21 +568,8 @@ def main(argv=None):
             got = queue.claim(1)
             if not got:
                 break
-            i = got[0]
-            std = T.load_data(patches[i])
-            if np.isclose(std, 0.0, atol=1e-12):
-                T.out_best, T.elapsed = T.img * T.mask, 0.0
-            else:
-                T.begin_patch(i)
-                if T.net is None or not args.start_from_prev:
-                    T.build_model(netpath=args.netdir[i]) if len(args.netdir) != 0 else T.build_model()
-                T.build_input()
-                T.build_regularizer()
-                T.optimize(verbose=False)
-            T.save_result()
-            _record_holdout(T, holdout_snrs)
-            T.clean()
-            mine.append(i)
+            T.run_patch(got[0], patches[got[0]], verbose=False)
+            _finish_patch(T, mine, holdout_snrs)
         if world > 1:
             dist.barrier()
         rec = reconstruct_patches(args) if rank == 0 else None

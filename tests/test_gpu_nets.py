@@ -628,13 +628,16 @@ def test_concurrent_patches_match_standalone_graph_run(tmp_path, monkeypatch):
     assert rec.shape == (40, 40, 40) and np.isfinite(rec).all()
 
 
+@pytest.mark.parametrize("schedule", ["rolling", "groups"])
 @pytest.mark.parametrize("early_stop", [False, True])
-def test_rolling_concurrency_slots_reproduce_the_sequential_driver(tmp_path, monkeypatch, early_stop):
+def test_rolling_concurrency_slots_reproduce_the_sequential_driver(tmp_path, monkeypatch, early_stop, schedule):
     """parallel._optimise_rolling (round 5: K concurrency slots kept full from the shared queue, a replay thread keeps the running patches'
     graphs going while the main thread sets up / captures / finishes patches) against main.main() (one patch after the other, reference
     main.py:274-295): every patch's best output, loss history and iteration count identical — a patch is seeded from its index and its
     graph replays the very kernels of the sequential run — and the same re-assembled volume.  8 patches through 3 slots, so slots are
-    re-filled while others run; with early stopping the patches end through the device-side `active` flag the main thread polls."""
+    re-filled while others run; with early stopping the patches end through the device-side `active` flag the main thread polls.
+    schedule "groups" (DPI_ROLLING_SLOTS=0) is the grouped schedule of optimise_volume on the same data: groups of three through
+    main.optimize_concurrently, the last group a short one of two."""
     import os
     from deep_prior_interpolation_amd import main as dmain, parallel, utils as u
     shape = (40, 40, 40)
@@ -650,6 +653,7 @@ def test_rolling_concurrency_slots_reproduce_the_sequential_driver(tmp_path, mon
         common += ["--earlystop_patience", "8", "--earlystop_min_delta", "3.0"]
     dmain.main(common + ["--outdir", "seq"])
     monkeypatch.setenv("DPI_CONCURRENT_PATCHES", "3")
+    monkeypatch.setenv("DPI_ROLLING_SLOTS", "1" if schedule == "rolling" else "0")
     monkeypatch.setenv("RANK", "0"); monkeypatch.setenv("WORLD_SIZE", "1"); monkeypatch.setenv("LOCAL_RANK", "0")
     parallel.main(common + ["--outdir", "roll"])
     names = sorted(f for f in os.listdir("results/seq") if f.endswith("_run.npy"))
