@@ -149,6 +149,9 @@ SIGNATURES = {
     # d / mask = [T][S] fp32, offset = [S] / vel = [NV] float64, num / den = [G][NV][T] float64, cnt the same as int32.  ABI_VERSION stays: a
     # stale library fails on the unresolved symbol
     "dpi_semblance_sums": (_I, [_P, _P, _P, _P, _I, C.c_double, _I, _Z, _I, _Z, _I, _Z, _P, _P, _P, _P]),
+    # --moveout_table device (ours): (law, offset, stretch, T, S, n_groups, group_stride, n_traces, trace_stride, table, stream); law =
+    # [G][T], offset = [S], table = [T][S], all float64; stretch 0 = none.  ABI_VERSION stays: a stale library fails on the unresolved symbol
+    "dpi_nmo_table": (_I, [_P, _P, C.c_double, _I, _I, _I, _I, _I, _I, _P, _P]),
     # --trace_offsets (ours): (x, off, C, T, X, Y, y, stream) and (y, off, C, T, X, Y, x, stream); off = [2][X][Y].  ABI_VERSION stays: a
     # stale library fails on the unresolved symbols
     "dpi_trace_sample_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),

@@ -59,7 +59,8 @@ def extract_patches(args) -> List[dict]:
     """List of {'image': patch*gain, 'mask': binary patch, 'name': zero-padded index} (data.py:44-84).  With --trace_offsets (ours) each
     dict gains 'offsets', the (X, Y, 2) window of the file (2-D: (X, 1, 2) with dy = 0) cut at the origin of its image and mask windows.
     With --moveout or --moveout_offset (ours) each dict gains 'moveout': all of t and the patch's x / y window of the table; with
-    --moveout_offset also 'moveout_velocity', the picked law (T,) of the volume or the laws (T, G_window) of the patch's gathers."""
+    --moveout_offset also 'moveout_velocity', the law (T,) of the volume or the laws (T, G_window) of the patch's gathers as used, and with
+    --moveout_smooth L > 0 'moveout_pick', the picked staircase(s) behind them in the same shape."""
     original = np.load(os.path.join(args.imgdir, args.imgname), allow_pickle=True)
     corrupted = np.load(os.path.join(args.imgdir, args.maskname), allow_pickle=True)
     assert original.shape == corrupted.shape, "Original and Corrupted data must have the same dimension"
@@ -89,6 +90,7 @@ def extract_patches(args) -> List[dict]:
     offs = _trace_offset_windows(args, off, original.shape, pe)
     movs = _moveout_windows(args, mov, original.shape, pe)
     laws = _velocity_windows(args, scan, original.shape, pe)
+    picks = _velocity_windows(args, scan, original.shape, pe, "pick") if scan.get("smooth", 0.0) > 0.0 else None
     width = u.ten_digit(img.shape[0])
     out = []
     for p in range(img.shape[0]):
@@ -102,6 +104,8 @@ def extract_patches(args) -> List[dict]:
             out[-1]["moveout"] = movs[p]
         if laws is not None:
             out[-1]["moveout_velocity"] = laws[p]
+        if picks is not None:
+            out[-1]["moveout_pick"] = picks[p]
     return out
 
 
@@ -195,21 +199,23 @@ def _scan_moveout(args, flags, vol_shape, pe, volume, mask, scan):
     known = np.asarray(mask) != 0
     try:
         res = scan_table(np.where(known, np.asarray(volume), 0.0), known, off, flags["vmin"], flags["vmax"], flags["nv"], gather=flags["gather"],
-                         window=flags["window"], min_fold=flags["min_fold"], max_step=flags["max_step"], stretch_mute=flags["stretch_mute"])
+                         window=flags["window"], min_fold=flags["min_fold"], max_step=flags["max_step"], stretch_mute=flags["stretch_mute"],
+                         smooth=flags.get("smooth", 0.0), table=flags.get("table", "host"))
     except ValueError as e:
         raise ValueError("--moveout_offset %s: %s" % (name, e)) from e
     if scan is not None:
-        scan.update(res, gather=flags["gather"])
+        scan.update(res, gather=flags["gather"], smooth=flags.get("smooth", 0.0))
     return check_moveout_table(res["table"], what="the table")[0]
 
 
-def _velocity_windows(args, scan, vol_shape, pe):
-    """The picked laws that belong to each image window (--moveout_offset), in the order of the image windows; None without a scan."""
+def _velocity_windows(args, scan, vol_shape, pe, key="velocity"):
+    """The laws that belong to each image window (--moveout_offset), in the order of the image windows; None without a scan.  `key`:
+    "velocity" = the laws as used, "pick" = the picked staircases behind them (--moveout_smooth)."""
     if not scan:
         return None
     from .operators.velocity import velocity_windows
     origins = u.window_origins(vol_shape, pe.dim, pe.stride, cover=reassembly_flags(args)[0])
-    return velocity_windows(scan["velocity"], scan["gather"], origins, pe.dim)
+    return velocity_windows(scan[key], scan["gather"], origins, pe.dim)
 
 
 def _moveout_windows(args, tab, vol_shape, pe):

@@ -59,6 +59,7 @@ class ForwardModel:
         self.pre = self.best = self._buffer = None               # the tracked stage's input: this iteration / selected / captured copy
         self.trace_offsets = self.live = None                    # per patch: (X, Y, 2) as used, i.e. zero at unknown traces / L's live map
         self.velocity = None                                     # per patch, --moveout_offset: (T,) or (T, G_window), the picked law(s)
+        self.pick = None                                         # per patch, --moveout_smooth: the staircase(s) behind the smoothed law(s)
 
     def stage(self, name):
         """The stage `name`, or None when there is none (its flag is off)."""
@@ -81,7 +82,8 @@ class ForwardModel:
         counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped)."""
         self._load_sampling(data.get("offsets"), shape, mask, name)
         self._load_moveout(data.get("moveout"), shape, name)
-        self.velocity = data.get("moveout_velocity")             # --moveout_offset: the picked law(s) behind the patch's table
+        self.velocity = data.get("moveout_velocity")             # --moveout_offset: the law(s) behind the patch's table
+        self.pick = data.get("moveout_pick")                     # --moveout_smooth: the picked staircase(s) behind the law(s)
         avo = self.stage("avo")
         if self.flags["avo"] is not None and (avo.op is None or avo.op.nt0 != int(shape[0])):       # kept while T stays the same
             from .operators import AVOLinearModelling
@@ -215,6 +217,11 @@ class ForwardModel:
                 # --moveout_offset: the picked law(s) the table was built from and the trial velocities [VMIN, VMAX, NV] of the scan
                 run.update(moveout_velocity=None if self.velocity is None else np.array(self.velocity, dtype=np.float64),
                            moveout_vscan=[float(v) for v in self.args.moveout_vscan])
+                smooth = float(getattr(self.args, "moveout_smooth", None) or 0.0)
+                if smooth > 0.0:                                 # the law above is the smoothed one: the length and the staircase behind it
+                    run.update(moveout_smooth=smooth, moveout_pick=None if self.pick is None else np.array(self.pick, dtype=np.float64))
+                if (getattr(self.args, "moveout_table", None) or "host") == "device":
+                    run["moveout_table"] = "device"
         if f["sampling"] is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
             run["trace_interp"] = self.trace_interp

@@ -1,17 +1,21 @@
 """Velocity estimation for --moveout (ours, --moveout_offset: the reference estimates no velocity).  A semblance scan over the known traces
 of a gather (`semblance_sums`, dpi_semblance_sums on the device: include/dpi_hip.h has the definition), the panel of the sums
-(`semblance_panel`), a picked law v(tau) per gather (`pick_velocity`, a Viterbi pass) and the NMO table of the pick (`scan_table`, through
-`nmo_table`).  Everything after the table is the path of --moveout.  The kernel sums in a fixed order and the host part is float64 numpy
+(`semblance_panel`), a picked law v(tau) per gather (`pick_velocity`, a Viterbi pass), optionally smoothed along tau (`smooth_law`,
+--moveout_smooth) and the NMO table of the law (`scan_table`, through `nmo_table` on the host or `nmo_table_device`, dpi_nmo_table, on the
+device).  Everything after the table is the path of --moveout.  The kernel sums in a fixed order and the host part is float64 numpy
 in a fixed order as well: the same data give the same table on every device and every rank."""
 import numpy as np
 import torch
 
 from .. import _lib
-from .moveout import check_moveout_table, nmo_table
+from .moveout import MOVEOUT_MUTE, check_moveout_table, nmo_table
 
-__all__ = ["GATHERS", "gather_geometry", "semblance_sums", "semblance_panel", "pick_velocity", "scan_table", "velocity_windows"]
+__all__ = ["GATHERS", "TABLE_BUILDERS", "NMO_TABLE_DEVICE_ROWS", "gather_geometry", "semblance_sums", "semblance_panel", "pick_velocity", "smooth_law",
+           "nmo_table_device", "scan_table", "velocity_windows"]
 
 GATHERS = ("volume", "x", "y")
+TABLE_BUILDERS = ("host", "device")
+NMO_TABLE_DEVICE_ROWS = 4096                # dpi_nmo_table keeps a trace's travel times in LDS: at most this many rows
 
 
 def gather_geometry(shape, gather="volume"):
@@ -118,18 +122,19 @@ def semblance_panel(num, den, cnt, window=2, min_fold=4):
     return np.ascontiguousarray(np.swapaxes(np.where(some, top / np.where(some, bot, 1.0), 0.0), 1, 2))
 
 
-def pick_velocity(panel, velocities, max_step=1):
+def pick_velocity(panel, velocities, max_step=1, return_index=False):
     """The law v(tau) of every gather, (G, T) float64: per gather the path j(tau) over the columns of its panel (T, NV) that maximises
     sum_tau P[tau, j(tau)] subject to |j(tau + 1) - j(tau)| <= max_step, found by a Viterbi pass in float64 (the scores are added in
     ascending tau).  Ties go to the lowest index: at the last row, and at every step back among the admissible predecessors.  Nothing is
-    smoothed across gathers."""
+    smoothed across gathers.  `return_index`: (the law, the path j (G, T) int64) instead of the law alone."""
     P = np.asarray(panel, dtype=np.float64)
     vel = np.asarray(velocities, dtype=np.float64).reshape(-1)
     if P.ndim != 3 or P.shape[2] != vel.size or P.size < 1:
         raise ValueError("panel must be (G, T, NV) with NV = %d velocities, got %s" % (vel.size, tuple(P.shape)))
     if int(max_step) != max_step or max_step < 0:
         raise ValueError("max_step must be an integer >= 0, got %r" % (max_step,))
-    return vel[_pick_index(P, int(max_step))]
+    path = _pick_index(P, int(max_step))
+    return (vel[path], path) if return_index else vel[path]
 
 
 def _pick_index(P, step):
@@ -155,11 +160,92 @@ def _pick_index(P, step):
     return path
 
 
-def scan_table(data, mask, offset, vmin, vmax, nv, gather="volume", window=2, min_fold=4, max_step=1, stretch_mute=None, device=None):
-    """Scan, pick and build the table: {"table": the float64 moveout table in the shape of `data` (operators.nmo_table on the picked law,
-    gather by gather, with the same `stretch_mute`; checked by check_moveout_table), "velocity": the picked laws (G, T), "velocities":
-    np.linspace(vmin, vmax, nv), "panel": (G, T, NV)}.  ValueError before any launch for vmin <= 0, vmax < vmin, nv < 1 and whatever
-    semblance_sums refuses; a picked law that makes a trace's table decrease along t raises one that names --moveout_vscan."""
+def smooth_law(law, weight, length):
+    """The laws (G, T) smoothed along tau by a Gaussian of `length` = L rows weighted by `weight` (G, T) >= 0, float64: with K = ceil(3 L)
+    and g_k = exp(-0.5 (k / L)^2), row tau becomes sum_k g_k w[r] v[r] / sum_k g_k w[r] over the rows r = tau + k, k = -K .. K, that lie
+    inside [0, T - 1] (the window is clipped, not replicated), both sums added in ascending k; where the weights of a window are all zero,
+    the unweighted sum_k g_k v[r] / sum_k g_k.  L = 0 returns `law` unchanged.  ValueError for shapes that do not match, negative or
+    non-finite weights and a negative or non-finite L."""
+    v = np.asarray(law, dtype=np.float64)
+    w = np.asarray(weight, dtype=np.float64)
+    if v.ndim != 2 or w.shape != v.shape or v.size < 1:
+        raise ValueError("law and weight must share one (G, T) shape, got %s and %s" % (tuple(v.shape), tuple(w.shape)))
+    L = float(length)
+    if not (np.isfinite(L) and L >= 0.0):
+        raise ValueError("the smoothing length must be finite and >= 0 (rows), got %r" % (length,))
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise ValueError("weight must be finite and >= 0")
+    if L == 0.0:
+        return v
+    T = v.shape[1]
+    K = min(int(np.ceil(3.0 * L)), T - 1)                        # rows further than T - 1 away lie outside every window
+    num, den, plain, norm = (np.zeros_like(v) for _ in range(4))
+    for k in range(-K, K + 1):
+        gk = np.exp(-0.5 * (k / L) ** 2)
+        lo, hi = max(0, -k), min(T, T - k)
+        gw = gk * w[:, lo + k:hi + k]
+        num[:, lo:hi] += gw * v[:, lo + k:hi + k]
+        den[:, lo:hi] += gw
+        plain[:, lo:hi] += gk * v[:, lo + k:hi + k]
+        norm[:, lo:hi] += gk
+    some = den > 0.0
+    return np.where(some, num / np.where(some, den, 1.0), plain / norm)
+
+
+def _check_laws(laws, G, T):
+    v = np.asarray(laws, dtype=np.float64)
+    if G == 1 and v.shape == (T,):
+        v = v[None]
+    if v.shape != (G, T):
+        raise ValueError("velocity must be %d values for each of the %d gathers, got %s" % (T, G, tuple(v.shape)))
+    if not np.all(np.isfinite(v)) or not np.all(v > 0.0):
+        raise ValueError("velocity must be finite and > 0 at every tau = 0 .. %d" % (T - 1))
+    return np.ascontiguousarray(v)
+
+
+def nmo_table_device(shape, offset, laws, gather="volume", stretch_mute=None, device=None):
+    """operators.nmo_table for sampled laws, built by dpi_nmo_table on the device (include/dpi_hip.h has the definition): the float64 table
+    of `shape` = (T, X) or (T, X, Y) for the laws (G, T) of the gathers of `gather` (gather_geometry; (T,) will do for one gather),
+    `offset` as in semblance_sums, one launch for all gathers.  The kernel forms the host's expressions in the host's order: the two
+    tables can differ only where the device rounds an fp64 square root or division differently.  ValueError before any launch for what
+    nmo_table refuses (shapes, non-finite offsets, a law that is not finite and > 0, a stretch mute that is not > 0) and for more than
+    NMO_TABLE_DEVICE_ROWS rows, which names --moveout_table."""
+    shape = tuple(int(n) for n in shape)
+    geo = gather_geometry(shape, gather)
+    off = _check_offset(offset, shape)
+    if stretch_mute is not None and not (float(stretch_mute) > 0.0 and np.isfinite(float(stretch_mute))):
+        raise ValueError("stretch_mute must be a finite value > 0, got %r" % (stretch_mute,))
+    T = shape[0]
+    S = int(np.prod(shape[1:]))
+    law = _check_laws(laws, geo[0], T)
+    if T > NMO_TABLE_DEVICE_ROWS:
+        raise ValueError("--moveout_table device builds tables of at most %d rows (a trace's travel times are kept in on-chip memory), got "
+                         "%d: use --moveout_table host" % (NMO_TABLE_DEVICE_ROWS, T))
+    if S >= (1 << 31):
+        raise ValueError("--moveout_table device: %d traces, at most 2^31 - 1: use --moveout_table host" % S)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        l_, o_ = torch.from_numpy(law).to(dev), torch.from_numpy(off.reshape(-1)).to(dev)
+        tab = torch.full((T, S), MOVEOUT_MUTE, dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().dpi_nmo_table(_lib.ptr(l_), _lib.ptr(o_), 0.0 if stretch_mute is None else float(stretch_mute), T, S, geo[0], geo[1],
+                                             geo[2], geo[3], _lib.ptr(tab), _lib.stream()), "dpi_nmo_table")
+        return tab.cpu().numpy().reshape(shape)
+
+
+def scan_table(data, mask, offset, vmin, vmax, nv, gather="volume", window=2, min_fold=4, max_step=1, stretch_mute=None, device=None,
+               smooth=0.0, table="host"):
+    """Scan, pick and build the table: {"table": the float64 moveout table in the shape of `data` (operators.nmo_table on the law, gather by
+    gather, with the same `stretch_mute`; checked by check_moveout_table), "velocity": the laws as used (G, T), "pick": the picked
+    staircase (G, T), "velocities": np.linspace(vmin, vmax, nv), "panel": (G, T, NV)}.  `smooth` = L > 0 (--moveout_smooth): the law as
+    used is smooth_law of the pick over L rows, weighted by the panel along the picked path; 0: the pick itself.  `table`: "host" =
+    nmo_table, "device" = nmo_table_device, one launch for all gathers.  ValueError before any launch for vmin <= 0, vmax < vmin, nv < 1,
+    a negative or non-finite `smooth`, an unknown `table` and whatever semblance_sums refuses; a law that makes a trace's table decrease
+    along t raises one that names --moveout_vscan."""
+    smooth = float(smooth)
+    if not (np.isfinite(smooth) and smooth >= 0.0):
+        raise ValueError("smooth must be finite and >= 0 (rows), got %r" % (smooth,))
+    if table not in TABLE_BUILDERS:
+        raise ValueError("table must be one of %s, got %r" % (", ".join(TABLE_BUILDERS), table))
     if int(nv) != nv or nv < 1:
         raise ValueError("nv must be an integer >= 1, got %r" % (nv,))
     vmin, vmax = float(vmin), float(vmax)
@@ -171,9 +257,14 @@ def scan_table(data, mask, offset, vmin, vmax, nv, gather="volume", window=2, mi
     shape = tuple(int(n) for n in np.shape(data))
     num, den, cnt = semblance_sums(data, mask, offset, vel, gather=gather, stretch_mute=stretch_mute, device=device)
     panel = semblance_panel(num, den, cnt, window=window, min_fold=min_fold)
-    law = pick_velocity(panel, vel, max_step=max_step)
+    pick, path = pick_velocity(panel, vel, max_step=max_step, return_index=True)
+    law = pick
+    if smooth > 0.0:
+        law = smooth_law(pick, np.take_along_axis(panel, path[:, :, None], axis=2)[:, :, 0], smooth)
     off = _check_offset(offset, shape)
-    if gather == "volume":
+    if table == "device":
+        table = nmo_table_device(shape, off, law, gather=gather, stretch_mute=stretch_mute, device=device)
+    elif gather == "volume":
         table = nmo_table(shape, off, law[0], stretch_mute)
     else:
         axis = 2 if gather == "y" else 1                         # the axis that numbers the gathers
@@ -184,7 +275,7 @@ def scan_table(data, mask, offset, vmin, vmax, nv, gather="volume", window=2, mi
     except ValueError as e:
         raise ValueError("--moveout_vscan: %s; a law that changes more slowly keeps the events of a trace in order: try a smaller "
                          "--moveout_max_step or a narrower scan" % e) from e
-    return {"table": table, "velocity": law, "velocities": vel, "panel": panel}
+    return {"table": table, "velocity": law, "pick": pick, "velocities": vel, "panel": panel}
 
 
 def velocity_windows(law, gather, origins, dim):

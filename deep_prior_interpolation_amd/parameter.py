@@ -183,6 +183,12 @@ _FLAGS = [
     (("--moveout_max_step",), dict(type=int, required=False,
                                   help="ours: most velocity steps the picked law of --moveout_offset changes by from one row to the "
                                        "next (default 1)")),
+    (("--moveout_smooth",), dict(type=float, required=False, metavar="L",
+                                help="ours: smooth the picked law of --moveout_offset along tau with a Gaussian of L rows, weighted by the "
+                                     "semblance on the picked path, before the table is built (absent = 0 = the staircase pick itself)")),
+    (("--moveout_table",), dict(type=str, required=False, choices=["host", "device"],
+                               help="ours: where the table of --moveout_offset is built from the law: host = operators.nmo_table (the "
+                                    "default), device = the same statements as one kernel launch for all gathers, at most 4096 rows")),
     # penalty on the tensor the network writes (ours: the reference has no prior on the model but the architecture)
     (("--model_reg",), dict(type=str, required=False, choices=list(MODEL_REG_KINDS),
                            help="ours: penalty on the tensor the network itself writes, before --avo_theta / --wavelet / --moveout map it to "
@@ -282,13 +288,15 @@ def check_wavelet(args: Namespace):
     return name, kind
 
 
-_VSCAN_ONLY = ("moveout_vscan", "moveout_gather", "moveout_stretch", "moveout_window", "moveout_min_fold", "moveout_max_step")
+_VSCAN_ONLY = ("moveout_vscan", "moveout_gather", "moveout_stretch", "moveout_window", "moveout_min_fold", "moveout_max_step", "moveout_smooth",
+               "moveout_table")
 
 
 def check_moveout_scan(args: Namespace):
     """--moveout_offset and its own flags; returns None when it is off (also for a Namespace without the keys), else the dict of what
-    operators.scan_table takes: file, vmin, vmax, nv, gather, stretch_mute, window, min_fold, max_step.  The flags of the scan are refused
-    without --moveout_offset, where they would silently do nothing."""
+    operators.scan_table takes: file, vmin, vmax, nv, gather, stretch_mute, window, min_fold, max_step, and, only where they differ from
+    the default, smooth (--moveout_smooth L > 0) and table (--moveout_table device).  The flags of the scan are refused without
+    --moveout_offset, where they would silently do nothing."""
     name = getattr(args, "moveout_offset", None)
     if name is None:
         given = [k for k in _VSCAN_ONLY if getattr(args, k, None) is not None]
@@ -324,6 +332,17 @@ def check_moveout_scan(args: Namespace):
         if int(v) != v or v < least:
             raise ValueError("--moveout_%s must be a whole number >= %d, got %r" % (key, least, v))
         out[key] = int(v)
+    smooth = getattr(args, "moveout_smooth", None)
+    if smooth is not None:
+        if not (float(smooth) >= 0.0 and float(smooth) < float("inf")):
+            raise ValueError("--moveout_smooth must be a finite length >= 0 (rows of tau), got %r" % (smooth,))
+        if float(smooth) > 0.0:
+            out["smooth"] = float(smooth)
+    builder = getattr(args, "moveout_table", None) or "host"
+    if builder not in ("host", "device"):
+        raise ValueError("--moveout_table must be host or device, got %r" % (builder,))
+    if builder == "device":
+        out["table"] = builder
     return out
 
 
@@ -483,6 +502,8 @@ _OURS_MUST_MATCH = (
     # the scanned table: what decides it (window, fold and step only tune the pick; the table itself is saved with the run)
     ("moveout_offset", None, _same), ("moveout_vscan", None, lambda v: None if v is None else [float(x) for x in v]),
     ("moveout_gather", "volume", _same), ("moveout_stretch", None, lambda v: None if v is None else float(v)),
+    # the law the table is built from, and where: the device's table may differ from the host's in the rounding of a square root
+    ("moveout_smooth", 0.0, float), ("moveout_table", "host", _same),
 )
 
 

@@ -699,6 +699,28 @@ int dpi_model_reg(const float* m, int C, size_t n0, size_t n1, size_t n2, int ax
 int dpi_semblance_sums(const float* d, const float* mask, const double* offset, const double* vel, int NV, double stretch, int T, size_t S,
                        int n_groups, size_t group_stride, int n_traces, size_t trace_stride, double* num, double* den, int* cnt, void* stream);
 
+/* ---------------------------------------------------------------- NMO table of sampled laws (--moveout_table device) --
+ * Ours: operators.nmo_table for laws given at tau = 0 .. T - 1, statement by statement and in its order of operations, all gathers in one
+ * launch.  law: [n_groups][T] float64 on the device, cells per sample, finite and > 0; offset: [S] float64 in cells; stretch: the stretch
+ * mute, 0 = none; table: [T][S] float64.  The geometry is that of dpi_semblance_sums: trace k of gather g is column g * group_stride +
+ * k * trace_stride, and every (g, k) must be a column of its own (the three layouts above name every column once; a column no (g, k)
+ * names is left untouched).  For the trace in column s of gather g, v = law[g], off = offset[s], everything in float64:
+ *     g[j] = sqrt(j^2 + (off / v[j])^2); jmin = the last index of its minimum; env[j] = max(g[jmin .. j]), -inf below jmin
+ *     j(t) = (the number of env <= t) - 1 clipped to [0, T - 2], for the recorded sample t = 0 .. T - 1
+ *     live iff j >= jmin, env[j] == g[j], env[j + 1] == g[j + 1], g[j + 1] > g[j], g[j] <= t <= g[j + 1] and (stretch == 0 or
+ *          1 / (g[j + 1] - g[j]) <= stretch)
+ *     56 bisection steps of [j, j + 1] on travel(x) = sqrt(x^2 + (off / vel(x))^2) <= t with vel(x) = v[j] at x == j, v[j + 1] at
+ *          x == j + 1, else (v[j + 1] - v[j]) * (x - j) + v[j]
+ *     table[t][s] = hi if travel(hi) == t else lo, clipped to [0, T - 1]; -1 (muted) where not live.  T = 1: 0 where off == 0, else -1.
+ * No fused multiply-add: the table can differ from the host's only through the rounding of the fp64 square root and division.  One
+ * workgroup per trace, g and env in LDS (16 T bytes), no atomics, one thread per output: repeated launches give the same bits.  No law
+ * or offset (NaN included: the sample is muted) reads or writes out of bounds.  A null pointer, table sharing memory with an input, T, S,
+ * n_groups or n_traces < 1, a negative or non-finite stretch, a stride < 1 where there is more than one gather / trace, a geometry
+ * whose last column is not below S and T > 4096 return an error before any launch.  ABI version stays: a stale library fails on the
+ * unresolved symbol. */
+int dpi_nmo_table(const double* law, const double* offset, double stretch, int T, int S, int n_groups, int group_stride, int n_traces,
+                  int trace_stride, double* table, void* stream);
+
 /* ---------------------------------------------------------------- Trace sampling (--trace_offsets) --
  * Ours (the reference takes every known trace to sit on a grid node): R samples a regular-grid tensor at the recorded trace positions,
  * bilinear in (x, y), the same for every t and every channel.  Tensor [C][T][X][Y] fp32 (a 2-D patch is Y = 1); offsets off = [2][X][Y]

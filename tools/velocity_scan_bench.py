@@ -9,6 +9,15 @@ NV x 2 reads = NV x one copy (one read and one write) is the time the bytes alon
 (max - min over the windows).  One JSON line for the copy and one per layout.
 
     python tools/velocity_scan_bench.py [--shape 256 128 128] [--nv 64] [--host-nv 4] [--runs 5] [--reps 5] [--warmup 2]
+
+--tables times the stage after the scan instead, the table build of a law per gather, for the three layouts: operators.nmo_table on this
+host, gather by gather as scan_table calls it (--parent-tree DIR: the function of that checkout, e.g. the commit this one is compared
+with; one build per layout, a host clock), against operators.nmo_table_device (--moveout_table device) with its copies to and from the
+device, a host clock around --reps calls that each end in a device-to-host copy, --runs windows after --warmup calls, the layouts
+alternating.  The floor beside them is one (T, S) float64 array copied from the device the same way.  Each line says whether the two
+tables have the same bits.
+
+    python tools/velocity_scan_bench.py --tables [--shape 256 128 128] [--runs 5] [--reps 3] [--warmup 2] [--stretch S] [--parent-tree DIR]
 """
 import argparse
 import json
@@ -45,6 +54,74 @@ def host_sums(d, known, off, vel, stretch, geo):
     return num, den, cnt
 
 
+def host_table(nmo_table, shape, off, laws, gather, stretch):
+    """The host path of operators.scan_table."""
+    if gather == "volume":
+        return nmo_table(shape, off, laws[0], stretch)
+    axis = 2 if gather == "y" else 1
+    return np.stack([nmo_table((shape[0], shape[3 - axis]), np.take(off, g, axis=axis - 1), laws[g], stretch) for g in range(shape[axis])], axis=axis)
+
+
+def tables(a):
+    import torch
+    from deep_prior_interpolation_amd.operators import GATHERS, gather_geometry, nmo_table_device
+    if not torch.cuda.is_available():
+        raise SystemExit("velocity_scan_bench needs a HIP device: a CPU cannot time this kernel")
+    torch.cuda.set_device(0)
+    if a.parent_tree:                                            # nmo_table of that checkout: its module alone, without its package
+        origin = os.path.join(os.path.abspath(a.parent_tree), "deep_prior_interpolation_amd", "operators", "moveout.py")
+        src = open(origin).read().replace("from .. import _lib", "_lib = None").replace("from .base import LinearOperator", "LinearOperator = object")
+        mod = {"__name__": "parent_moveout_tables"}
+        exec(compile(src, origin, "exec"), mod)
+        nmo_table = mod["nmo_table"]
+    else:
+        from deep_prior_interpolation_amd.operators import nmo_table
+    shape = tuple(a.shape)
+    T, X, Y = shape
+    off = T * np.sqrt((np.arange(X)[:, None] / X) ** 2 + (np.arange(Y)[None, :] / Y) ** 2)
+    rng = np.random.RandomState(0)
+    grid = np.linspace(1.0, 1.8, 33)
+    laws = {}
+    for k in GATHERS:                                            # staircase picks: a walk of at most one grid step per row, one per gather
+        G = gather_geometry(shape, k)[0]
+        laws[k] = grid[np.clip(np.cumsum(rng.randint(-1, 2, (G, T)), axis=1) + 12, 0, 32)]
+    dev = lambda k: nmo_table_device(shape, off, laws[k], gather=k, stretch_mute=a.stretch)
+    flat = torch.zeros((T, X * Y), dtype=torch.float64, device="cuda")
+    variants = {k: (lambda k=k: dev(k)) for k in GATHERS}
+    variants["copy"] = lambda: flat.cpu().numpy()
+
+    def window(fn):
+        torch.cuda.synchronize()
+        t0 = perf_counter()
+        for _ in range(a.reps):
+            fn()                                                 # ends in a device-to-host copy: synchronous
+        return (perf_counter() - t0) * 1e3 / a.reps              # milliseconds per build
+
+    for fn in variants.values():
+        for _ in range(a.warmup):
+            fn()
+    ms = {k: [] for k in variants}
+    for r in range(a.runs):
+        for k in (list(variants) if r % 2 == 0 else list(variants)[::-1]):
+            ms[k].append(window(variants[k]))
+    stat = lambda q: {"per_run": [round(x, 3) for x in q], "mean": round(float(np.mean(q)), 3), "spread": round(float(np.max(q) - np.min(q)), 3)}
+    head = {"shape": a.shape, "runs": a.runs, "reps": a.reps, "stretch": a.stretch, "gpu": torch.cuda.get_device_name(0),
+            "host": "parent tree" if a.parent_tree else "this tree"}
+    copy = float(np.mean(ms["copy"]))
+    print(json.dumps(dict(head, variant="copy_of_one_table_to_the_host", ms=stat(ms["copy"]), GBps=round(8 * flat.numel() / copy / 1e6, 2))), flush=True)
+    for k in GATHERS:
+        t0 = perf_counter()
+        want = host_table(nmo_table, shape, off, laws[k], k, a.stretch)
+        host_s = perf_counter() - t0
+        got = dev(k)
+        live = want != -1.0
+        mean = float(np.mean(ms[k]))
+        print(json.dumps(dict(head, variant=k, gathers=int(laws[k].shape[0]), device_ms=stat(ms[k]), host_s=round(host_s, 3),
+                              times_faster_than_host=round(host_s * 1e3 / mean, 1), times_the_copy=round(mean / copy, 2),
+                              live_share=round(float(live.mean()), 4), live_maps_equal=bool(np.array_equal(got != -1.0, live)),
+                              bit_identical=bool(np.array_equal(got, want)), max_abs_diff=float(np.max(np.abs(got - want))))), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--shape", type=int, nargs=3, default=[256, 128, 128], help="T X Y")
@@ -54,7 +131,11 @@ def main():
     p.add_argument("--runs", type=int, default=5)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--tables", action="store_true", help="time the table build (host nmo_table against nmo_table_device) instead of the scan")
+    p.add_argument("--parent-tree", default=None, help="--tables: a checkout whose operators.nmo_table is the host side")
     a = p.parse_args()
+    if a.tables:
+        return tables(a)
     import torch
     from deep_prior_interpolation_amd import _lib, utils as u
     from deep_prior_interpolation_amd.operators import GATHERS, gather_geometry
