@@ -3,7 +3,11 @@
 (d = W G m, d = L m), so everything that keeps an output sees a data-domain tensor; the "data" stage R follows only on the way to the
 misfit, so everything that keeps an output keeps the grid tensor.  W and L cannot be inverted: their stage is `tracked`, i.e. its input
 is kept beside the output when an iterate is selected (`pre` / `best`).  G is not tracked: every selected output, an average of iterates
-included, is a linear combination of iterates G m_i, and the pseudo-inverse returns the same combination of the m_i."""
+included, is a linear combination of iterates G m_i, and the pseudo-inverse returns the same combination of the m_i.
+The order rule: W and L together need --wavelet_domain, which orders them: "model" keeps the order above (d = L W r, the wavelet
+stretches with the events), "data" is avo, moveout, wavelet (d = W L r, the wavelet acts in recorded time).  There is still one
+pre / best pair: it holds the input of the FIRST of the two, the tensor the network writes, and the section in front of the second
+one is the first operator applied to it when the result is asked for."""
 import os
 from dataclasses import dataclass
 
@@ -12,9 +16,10 @@ import torch
 
 from . import _lib
 from . import utils as u
-from .parameter import check_avo, check_moveout, check_trace_offsets_flag, check_wavelet
+from .parameter import check_avo, check_moveout, check_trace_offsets_flag, check_wavelet, check_wavelet_domain
 
-ORDER = ("avo", "wavelet", "moveout", "sampling")
+ORDER = ("avo", "wavelet", "moveout", "sampling")              # the default, and --wavelet_domain model
+ORDER_DATA = ("avo", "moveout", "wavelet", "sampling")         # --wavelet_domain data
 
 
 @dataclass
@@ -34,13 +39,18 @@ class ForwardModel:
     """Built once per Interpolator from `args` (the four check_* of parameter.py decide which stages there are; the wavelet is read from
     --imgdir here), loaded once per patch (load_patch), applied every iteration (apply_model, apply_data).  `stages` adds or replaces
     stages with ready-made ones.  A fifth operator is a check_* result in `flags`, a Stage in __init__, its per-patch part in
-    load_patch and its keys in run_fields."""
+    load_patch and its keys in run_fields; if it is tracked and may meet W or L, it also needs its place in both orders (ORDER,
+    ORDER_DATA): two tracked stages are accepted only when the args carry a --wavelet_domain, the first of them owns pre / best, and
+    model() of the second is the first one's operator applied to `best`.  W and L themselves stay two stages, so each keeps its name,
+    its keys and its model; with both, load_patch joins their operators in one operators.PrestackModelling (`pair`), which runs the
+    iteration in their place (one autograd node: the tensor between them is not kept for the backward pass) and whose `live` is the map."""
 
     def __init__(self, args, stages=()):
         self.args = args
         # None when the flag is off, else: (theta, vsvp, linearization) / (file name, kind) / (file name, interp) / file name
         self.flags = {"avo": check_avo(args), "wavelet": check_wavelet(args), "moveout": check_moveout(args),
                       "sampling": check_trace_offsets_flag(args)}
+        self.domain = check_wavelet_domain(args)                 # --wavelet_domain: "data" | "model", None = undecided
         self.trace_interp = getattr(args, "trace_interp", None) or "linear"     # --trace_interp: the kernel R samples with (linear = bilinear)
         # --out_ema and the samplers select an average of iterates, whose model is not tracked
         self.averaged = (getattr(args, "out_ema", 0.0) or 0.0) > 0.0 or getattr(args, "optimizer", "adam") != "adam"
@@ -49,15 +59,18 @@ class ForwardModel:
         if "wavelet" in by_name:
             by_name["wavelet"].op = self._read_wavelet()
         by_name.update((s.name, s) for s in stages)
-        self.stages = sorted(by_name.values(), key=lambda s: ORDER.index(s.name))
+        order = ORDER_DATA if self.domain == "data" else ORDER
+        self.stages = sorted(by_name.values(), key=lambda s: order.index(s.name))
         tracked = [s.name for s in self.stages if s.tracked]
-        if len(tracked) > 1:
+        if len(tracked) > 1 and self.domain is None:
             raise ValueError("the stages %s both keep their input for the selected iterate: there is one pre / best pair, and which of "
                              "the two operators comes first is not decided yet" % " and ".join(tracked))
+        self._tracked = [s for s in self.stages if s.tracked]
         self._model = [s for s in self.stages if s.domain == "model"]
         self._data = [s for s in self.stages if s.domain == "data"]
-        self.pre = self.best = self._buffer = None               # the tracked stage's input: this iteration / selected / captured copy
-        self.trace_offsets = self.live = None                    # per patch: (X, Y, 2) as used, i.e. zero at unknown traces / L's live map
+        self.pre = self.best = self._buffer = None               # the first tracked stage's input: this iteration / selected / captured copy
+        self.trace_offsets = self.live = None                    # per patch: (X, Y, 2) as used, i.e. zero at unknown traces / the live map
+        self.pair = None                                         # per patch, W and L together: their PrestackModelling
         self.velocity = None                                     # per patch, --moveout_offset: (T,) or (T, G_window), the picked law(s)
         self.pick = None                                         # per patch, --moveout_smooth: the staircase(s) behind the smoothed law(s)
 
@@ -79,7 +92,9 @@ class ForwardModel:
         """The per-patch stages of the patch dict `data` with image shape `shape` (numpy order, channels last) and host mask `mask`;
         every stage goes to `device` here, before iteration 0, so a captured iteration replays the stages unchanged.  Returns the
         boolean map (T, X[, Y]) of the samples L leaves live, or None: the caller multiplies it into the DEVICE mask, so a muted sample
-        counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped)."""
+        counts in no loss, SNR or hold-out draw (and a patch without a live known sample has std 0: skipped).  Under --wavelet_domain
+        data the map is L's eroded along t by the reach of the wavelet (operators.erode_live): W reads the zeros L writes at muted
+        samples, and a data sample next to a mute would be compared with a truncated convolution."""
         self._load_sampling(data.get("offsets"), shape, mask, name)
         self._load_moveout(data.get("moveout"), shape, name)
         self.velocity = data.get("moveout_velocity")             # --moveout_offset: the law(s) behind the patch's table
@@ -91,7 +106,26 @@ class ForwardModel:
             avo.op = AVOLinearModelling(theta, vsvp=vsvp, nt0=int(shape[0]), spatdims=(1,), linearization=lin)
         for s in self.stages:
             s.op.upload(device)
+        self._join_pair(device)
         return self.live
+
+    def _join_pair(self, device):
+        """W and L of this patch as one operator in the order of --wavelet_domain: it takes their place in the iteration and its live
+        map is the patch's.  Stand-in stages (the `stages` of __init__) stay two."""
+        from .operators import ConvolutionalModelling, Moveout, PrestackModelling
+        self.pair = None
+        self._model = [s for s in self.stages if s.domain == "model"]
+        wav, mov = self.stage("wavelet"), self.stage("moveout")
+        if self.domain is None or wav is None or mov is None:
+            return
+        if not (isinstance(wav.op, ConvolutionalModelling) and isinstance(mov.op, Moveout)):
+            return
+        self.pair = PrestackModelling(wav.op, mov.op, domain=self.domain)
+        self.pair.upload(device)
+        self.live = self.pair.live
+        i = min(self._model.index(wav), self._model.index(mov))
+        assert abs(self._model.index(wav) - self._model.index(mov)) == 1, "W and L must be neighbours in ORDER and ORDER_DATA"
+        self._model[i:i + 2] = [Stage("prestack", self.pair, "model", True)]
 
     def _load_sampling(self, offsets, shape, mask, name):
         """--trace_offsets: the patch's (X, Y, 2) offsets -> R.  Offsets of traces the mask marks unknown are zeroed: the operator is
@@ -143,9 +177,11 @@ class ForwardModel:
     # ---- per iteration -----------------------------------------------------------------------------------------
     def apply_model(self, out):
         """The network's output -> the data-domain tensor that everything downstream keeps and compares."""
+        kept = False
         for s in self._model:
-            if s.tracked:
+            if s.tracked and not kept:                           # the first tracked stage: what the network writes (behind G)
                 self.pre = out.detach()                          # kept when this iterate is selected
+                kept = True
             out = s.op(out)
         return out
 
@@ -184,8 +220,10 @@ class ForwardModel:
     def model(self, name, out_best=None):
         """The section behind the selected output for stage `name`, in the numpy order and shape of `output`, in the patch's gained
         units.  A tracked stage: its input at the selected iteration; None for a patch that was not optimised, and with --out_ema or a
-        sampler.  "avo": m_t = pinv(G_t) out_best_t per time sample in float64 with the fp32 G of the device, stored as fp32, from
-        the selected output `out_best` (numpy; None for a patch that was not optimised)."""
+        sampler.  The second of two tracked stages (--wavelet_domain): the first one's operator applied to the kept tensor, now, with
+        the operator object and the kernel of the iteration, so it has the bits the iteration saw.  "avo": m_t = pinv(G_t) out_best_t
+        per time sample in float64 with the fp32 G of the device, stored as fp32, from the selected output `out_best` (numpy; None for a
+        patch that was not optimised)."""
         st = self.stage(name)
         if st is None or st.op is None:
             return None
@@ -196,7 +234,10 @@ class ForwardModel:
             return avo_model_from_data(out_best, st.op.G.numpy().reshape(st.op.ntheta, 3, st.op.nt0)).astype(np.float32)
         if not st.tracked or self.best is None or self.averaged:
             return None
-        return to_numpy_out(self.best)
+        if st is self._tracked[0]:
+            return to_numpy_out(self.best)
+        with torch.no_grad():
+            return to_numpy_out(self._tracked[0].op(self.best))
 
     def run_fields(self, out_best=None):
         """What the result file says about the stages (merged into `run` by save_result)."""
@@ -222,6 +263,8 @@ class ForwardModel:
                     run.update(moveout_smooth=smooth, moveout_pick=None if self.pick is None else np.array(self.pick, dtype=np.float64))
                 if (getattr(self.args, "moveout_table", None) or "host") == "device":
                     run["moveout_table"] = "device"
+        if self.domain is not None:
+            run["wavelet_domain"] = self.domain                  # d = W L r (data) or d = L W r (model): which model is which
         if f["sampling"] is not None:
             run["trace_offsets"] = self.trace_offsets            # (X, Y, 2) as used: zero at unknown traces; `output` is the grid tensor
             run["trace_interp"] = self.trace_interp

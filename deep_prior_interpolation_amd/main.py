@@ -329,7 +329,8 @@ class Interpolator:
         channel (amax over dim 1: the 2.5-D slab's channels; in 3-D the mask itself).  Constant per patch: built once, so a captured
         iteration replays it unchanged.  With --avo_theta the network writes three parameter sections and the AVO operator behind it maps
         them to the patch's angle sections; with --wavelet the wavelet operator comes last (d = W G m); with --moveout the network writes
-        the flattened gather and the moveout operator comes last (d = L m): what this returns is a data-domain tensor either way."""
+        the flattened gather and the moveout operator comes last (d = L m); with both, --wavelet_domain orders them (d = W L r or
+        d = L W r): what this returns is a data-domain tensor either way."""
         m = self._net_forward(z)
         if self.model_reg is not None:
             # --model_reg: what the network wrote is kept with its graph until model_regularization() takes it.  Without the flag nothing

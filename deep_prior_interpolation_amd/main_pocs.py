@@ -38,6 +38,9 @@ class Interpolator(_Base):
         if getattr(args, "trace_offsets", None) is not None:
             raise ValueError("main_pocs does not support --trace_offsets: the POCS projection re-inserts the traces at their grid nodes, "
                              "which is the assumption the flag removes; run main.py")
+        if getattr(args, "wavelet_domain", None) is not None:
+            raise ValueError("main_pocs does not support --wavelet_domain: it orders --wavelet and --moveout, neither of which the POCS "
+                             "projection can sit behind; run main.py")
         if getattr(args, "wavelet", None) is not None:
             raise ValueError("main_pocs does not support --wavelet: the POCS projection re-inserts the known traces into the output, which "
                              "takes it out of the range of the wavelet operator; run main.py")

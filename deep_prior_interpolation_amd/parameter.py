@@ -150,6 +150,11 @@ _FLAGS = [
     (("--wavelet_model",), dict(type=str, required=False, default="reflectivity", choices=["reflectivity", "impedance"],
                                help="ours: what the network writes under --wavelet: reflectivity = r, traces d = w * r; impedance = m = ln(AI), "
                                     "traces d = 0.5 w * D m with D the forward difference along t; needs --wavelet")),
+    (("--wavelet_domain",), dict(type=str, required=False, choices=["data", "model"],
+                                help="ours: where the wavelet acts when --wavelet meets --moveout or --moveout_offset (absent = undecided: the "
+                                     "pair is refused): data = d = W L r, the wavelet is applied in recorded time behind the moveout and is not "
+                                     "stretched (the pre-stack convolutional model of a recorded gather); model = d = L W r, the wavelet is "
+                                     "applied in zero-offset time and stretches with the events; needs --wavelet and a moveout flag")),
     # moveout along t (ours: the reference warps no axis)
     (("--moveout",), dict(type=str, required=False,
                          help="ours: a .npy in --imgdir with a moveout table tau (absent = off): (T, X, Y) for --datadim 3d on a (T, X, Y) "
@@ -238,6 +243,7 @@ def postprocess(args: Namespace) -> Namespace:
     check_avo(args)
     check_wavelet(args)
     check_moveout(args)
+    check_wavelet_domain(args)
     check_model_reg(args)
     return args
 
@@ -368,8 +374,9 @@ def check_moveout(args: Namespace):
         raise ValueError("%s needs --datadim 2d or 3d, got --datadim %s: a 2.5-D slab is not served" % (flag, args.datadim))
     if getattr(args, "avo_theta", None) is not None:
         raise ValueError("%s does not combine with --avo_theta, which needs --datadim 2.5d" % flag)
-    if getattr(args, "wavelet", None) is not None:
-        raise ValueError("%s does not combine with --wavelet: which of the two operators comes first is not decided yet" % flag)
+    if getattr(args, "wavelet", None) is not None and getattr(args, "wavelet_domain", None) is None:
+        raise ValueError("%s does not combine with --wavelet: which of the two operators comes first is not decided yet.  "
+                         "--wavelet_domain data | model decides it" % flag)
     if getattr(args, "net", "multiunet") == "part":
         raise ValueError("%s does not combine with --net part: its hole map would live on the model's time axis, the mask on the "
                          "data's" % flag)
@@ -377,6 +384,24 @@ def check_moveout(args: Namespace):
         raise ValueError("%s does not combine with --data_forgetting_factor %d: it adds data-domain traces to the input of a "
                          "network that writes the model domain" % (flag, args.data_forgetting_factor))
     return name, interp
+
+
+def check_wavelet_domain(args: Namespace):
+    """--wavelet_domain and what it needs; returns None when it is absent (also for a Namespace without the key, as those of older
+    args.txt files), else "data" (d = W L r) or "model" (d = L W r).  The flag is refused without both of its partners, where it would
+    silently do nothing; the pair without the flag is refused by check_moveout."""
+    domain = getattr(args, "wavelet_domain", None)
+    if domain is None:
+        return None
+    if domain not in ("data", "model"):
+        raise ValueError("--wavelet_domain must be data or model, got %r" % (domain,))
+    missing = [flag for flag, on in (("--wavelet", getattr(args, "wavelet", None) is not None),
+                                     ("--moveout or --moveout_offset", getattr(args, "moveout", None) is not None
+                                      or getattr(args, "moveout_offset", None) is not None)) if not on]
+    if missing:
+        raise ValueError("--wavelet_domain %s needs %s: it orders the two operators, and with one of them nothing is ordered and the "
+                         "flag would silently do nothing" % (domain, " and ".join(missing)))
+    return domain
 
 
 def model_reg_axes(kind, datadim, slice):
@@ -504,6 +529,7 @@ _OURS_MUST_MATCH = (
     ("moveout_gather", "volume", _same), ("moveout_stretch", None, lambda v: None if v is None else float(v)),
     # the law the table is built from, and where: the device's table may differ from the host's in the rounding of a square root
     ("moveout_smooth", 0.0, float), ("moveout_table", "host", _same),
+    ("wavelet_domain", None, _same),                             # which of W and L comes first: what the network's output means
 )
 
 
